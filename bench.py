@@ -4,10 +4,16 @@ step) on MI355X: ResNet-34 + geometric head + Patch-PnP, 256x256 RoIs, bs=64 per
 configs[1] = LM-13 `a6_cPnP_lm13`, bf16 operands / fp32 accumulate), synthetic seeded RoI batch resident
 in HBM, random-init (deterministic Kaiming-scaled) weights.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-One JSON line on rank 0.  `roofline`: the conv kernel instantiation with the largest share of the step (picked live;
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, ...);
+`--dump-outputs DIR` then runs the timed step function once more from the seeded start (weights, fresh optimizer state, batch) and writes
+what it computed (bench.py::step_outputs) as DIR/<name>.npy before the line is printed; two runs agree to the last bit but for a few 1-ulp
+parameters.  The timed model's own last step is not reproducible: the fp32-atomic weight-gradient sums differ in the last bits from run to
+run, and over W + N steps the random-init network amplifies that until two runs' poses part (R 0.77 apart at the defaults).
+`--full` adds the measurements below, each outside the timed region (`--no-roofline`, `--no-cpu-baseline`, `--no-extras` leave parts out):
+`roofline`: the conv kernel instantiation with the largest share of the step (picked live;
 currently the halo-tiled 3x3 kernel, 8x16 pixels x 128 channels) -- every launch of it in one step is bracketed by HIP
 events on the launch stream; achieved = sum(algorithmic FLOPs) / sum(durations - event overhead) against the
 2.5 PFLOP/s dense bf16 MFMA peak.
@@ -39,6 +45,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--bs", type=int, default=64, help="RoIs per GPU")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also roofline, cpu_baseline, parity and the extra loops (also, fp32_parity_mode); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the step once from the seeded start and write what it computed as DIR/<name>.npy "
+                         "(float32; larger arrays as a fixed seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-threads-sweep", action="store_true",
@@ -142,6 +153,8 @@ def dry_main(args):
         t = torch.tensor([dt, 0.0 if ok else 1.0], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, ok = float(t[0]), float(t[1]) == 0.0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"grad_flat": flat})   # what the exchange left in the flat gradient buffer
     if rank == 0:
         print(json.dumps({"metric": "RoI crops/sec (fwd+bwd) at 256\u00d7256 bs=64", "value": round(world * args.bs * args.steps / dt, 2), "unit": "RoI/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -178,6 +191,45 @@ def _cpu_model():
 
 def _pose_outputs(o):
     return {k: o[k].detach().float().cpu() for k in ("rot6d", "t_", "rot", "trans")}
+
+
+DUMP_CAP = 1 << 22        # elements of one dumped array (16 MB in float32); a larger one is written as a fixed, seeded sample
+DUMP_LIMIT = 64 << 20     # bytes of one dump in all
+
+
+def step_outputs(model, out, B, fwd_only):
+    """what one step handed its caller.  Training step: the [8] weighted losses train_step returns (order engine.LOSS_NAMES),
+    the pose of its forward pass (R, t), the parameters the optimizer step left (flattened in named_parameters() order) and the BatchNorm
+    running statistics.  Inference (--fwd-only): the forward's output dict."""
+    import torch
+
+    if fwd_only:
+        return dict(out)
+    plan = model.engine().plan(B, True, True)
+    return {"losses": out, "rot": plan.rot[:B], "trans": plan.trans[:B],
+            "params": torch.cat([p.detach().float().reshape(-1) for _, p in model.named_parameters()]),
+            "bn_running_stats": torch.cat([b.detach().float().reshape(-1) for b in model.buffers() if b.is_floating_point()])}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy in float32 per array; an array of more than DUMP_CAP elements is flattened and only the elements at
+    DUMP_CAP positions drawn with seed 0 (sorted) are written -- the same positions in every run of the same configuration"""
+    import numpy as np
+    import torch
+
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_CAP, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:   # checked before any file is written: no partial dump
+        raise ValueError(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT >> 20} MB")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(parity_bs=None):
@@ -517,23 +569,30 @@ def main():
             os.environ.setdefault("GDRN_BUCKETS", "5")  # (the engine picks this itself once the group exists; explicit for clarity)
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device(dev))
 
-    cfg = lm13_cfg(device=dev)
-    cfg.MODEL.CDPN.HIP_DTYPE = args.dtype
-    model, opt = GDRN.build_model_optimizer(cfg)
-    model.load_state_dict(synth.make_state_dict(0))
+    def make_model():
+        cfg = lm13_cfg(device=dev)
+        cfg.MODEL.CDPN.HIP_DTYPE = args.dtype
+        m, o = GDRN.build_model_optimizer(cfg)
+        m.load_state_dict(synth.make_state_dict(0))
+        return m, o
+
+    def attach(m):
+        gdist.broadcast_parameters(m)
+        m.train()
+        gdist.attach(m, force=args.dist_force, comm_dtype=args.comm_dtype)
+
+    model, opt = make_model()
     B = args.bs
     batch = synth.make_batch(B, seed=1 + rank)  # each rank its own RoIs (weak scaling)
     batch = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
     kw = synth.model_kwargs(batch, do_loss=not args.fwd_only)
     kw.pop("do_loss")
     if use_dist:
-        gdist.broadcast_parameters(model)
-        model.train()
-        gdist.attach(model, force=args.dist_force, comm_dtype=args.comm_dtype)
+        attach(model)
 
     # parity of what is timed: the pose outputs of one train-mode forward of every arithmetic the line reports, on fresh
     # weights, kept on the host until the cpu_baseline leg has the oracle's outputs for the same batch
-    want_parity = world == 1 and not args.fwd_only and not args.no_cpu_baseline and B in (4, 64)
+    want_parity = args.full and world == 1 and not args.fwd_only and not args.no_cpu_baseline and B in (4, 64)
     probes = {}
 
     def pose_probe(m):
@@ -555,17 +614,21 @@ def main():
         probes["plain"] = pose_probe(model)
         model.load_state_dict(synth.make_state_dict(0))   # (the probe's forward moved the BatchNorm running statistics)
 
-    if args.fwd_only:
-        model.eval()
+    def make_step(m, o):
+        if args.fwd_only:
+            m.eval()
 
-        def step():
-            with torch.no_grad():
-                return model(batch["roi_img"], do_loss=False, **kw)
-    else:
-        model.train()
+            def step():
+                with torch.no_grad():
+                    return m(batch["roi_img"], do_loss=False, **kw)
+        else:
+            m.train()
 
-        def step():
-            return model.train_step(batch["roi_img"], optimizer=opt, **kw)
+            def step():
+                return m.train_step(batch["roi_img"], optimizer=o, **kw)
+        return step
+
+    step = make_step(model, opt)
 
     for _ in range(args.warmup):
         out = step()
@@ -587,11 +650,25 @@ def main():
         dt = float(t.item())
     if not args.fwd_only:
         assert torch.isfinite(out).all(), out
+    if args.dump_outputs:
+        # not the timed model's own last step: its weights come out of W + N - 1 updates whose 1x1-conv and stem weight gradients are summed
+        # with fp32 atomics in completion order, and the random-init network with batch-statistics BatchNorm amplifies such last-bit
+        # differences until two runs part (measured at the defaults: R of the last step 0.77 apart, losses 5 %).  The same step function
+        # from the seeded weights, a fresh optimizer state and the same batch has inputs that are identical in every run
+        md, od = make_model()
+        if use_dist:
+            attach(md)
+        out_d = make_step(md, od)()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, step_outputs(md, out_d, B, args.fwd_only))
+        del md, od, out_d
+        torch.cuda.empty_cache()
 
     # SURVEY section 8(d) also asks for the step without the optimizer and for forward-only inference: short extra loops
     # OUTSIDE the timed region above (single GPU only, reported under "also")
     also = None
-    if world == 1 and not args.fwd_only and not args.no_extras:
+    if args.full and world == 1 and not args.fwd_only and not args.no_extras:
         def timed(fn, n):
             for _ in range(3):
                 fn()
@@ -674,7 +751,7 @@ def main():
         }
         if also is not None:
             res["also"] = also
-        if not args.no_roofline and not args.fwd_only:
+        if args.full and not args.no_roofline and not args.fwd_only:
             eng = model.engine()
             plan = eng.plan(B, True, True)
             a = {k: kw.get(k) for k in ("gt_xyz", "gt_mask_trunc", "gt_mask_visib", "gt_region", "gt_ego_rot", "gt_points", "sym_infos",
@@ -684,7 +761,7 @@ def main():
             res["roofline"] = measure_roofline(model, plan, kctx, args.dtype)
         if also is not None and "fp32_parity_mode" in also:
             res["fp32_parity_mode"] = also.pop("fp32_parity_mode")   # a sibling of `roofline`: the arithmetic the 1e-4 pose bound belongs to
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb = cpu_baseline(parity_bs=B if want_parity else None)
             ref = cb.pop("__ref_pose__")
             res["cpu_baseline"] = cb

@@ -284,6 +284,43 @@ def test_bench_gpus2_launches_its_own_ranks_dry_gloo():
     assert j["config"]["global_batch"] == 128 and j["value"] > 0 and j["steps"] == 2 and j["warmup"] == 1
 
 
+def test_bench_dump_outputs_dry(tmp_path):
+    """--dump-outputs DIR writes what the timed steps left (--dry: the flat gradient buffer after the exchange) as float32 .npy; an array
+    larger than bench.DUMP_CAP (2^22) elements is written as a seeded sample of that many elements, the same one in every run."""
+    import numpy as np
+
+    got = []
+    for run in ("a", "b"):
+        rc, j = _bench("--gpus", "1", "--backend", "gloo", "--dry", "--steps", "3", "--warmup", "1", "--bs", "8", "--dump-outputs", str(tmp_path / run))
+        assert rc == 0 and j["protocol_ok"] is True and j["steps"] == 3 and j["ms_per_step"] > 0, j
+        a = np.load(tmp_path / run / "grad_flat.npy")
+        assert a.dtype == np.float32 and a.shape == (1 << 22,) and (a == 1.0).all()   # one rank: every gradient element holds rank + 1
+        got.append(a)
+    assert np.array_equal(*got)
+
+
+def test_dump_outputs_samples_fixed_positions_and_writes_nothing_over_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: an array above DUMP_CAP elements keeps exactly the seed-0 positions, sorted, in every call; a smaller one is written
+    whole with its shape; a dump above DUMP_LIMIT is refused before any file is written."""
+    import numpy as np
+
+    monkeypatch.setenv("GPU_MAX_HW_QUEUES", os.environ.get("GPU_MAX_HW_QUEUES", "4"))   # (bench sets a default for its own process)
+    import bench
+
+    n = bench.DUMP_CAP + 12345
+    want = np.sort(np.random.default_rng(0).choice(n, bench.DUMP_CAP, replace=False))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"big": torch.arange(n, dtype=torch.float64), "small": torch.arange(6.0).view(2, 3)})
+        big = np.load(tmp_path / run / "big.npy")
+        assert big.dtype == np.float32 and np.array_equal(big, want.astype(np.float32))   # value = position (exact below 2^24)
+        small = np.load(tmp_path / run / "small.npy")
+        assert small.dtype == np.float32 and np.array_equal(small, np.arange(6.0).reshape(2, 3))
+    parts = {f"p{i}": torch.zeros(bench.DUMP_CAP) for i in range(bench.DUMP_LIMIT // (4 * bench.DUMP_CAP) + 1)}
+    with pytest.raises(ValueError, match="MB"):
+        bench.dump_outputs(str(tmp_path / "over"), parts)
+    assert not (tmp_path / "over").exists()
+
+
 @pytest.mark.skipif(torch.cuda.is_available() and torch.cuda.device_count() >= 2, reason="box has two GPUs: the launch would really run")
 def test_bench_gpus2_without_two_gpus_is_one_json_error_line():
     rc, j = _bench("--gpus", "2", "--steps", "2", "--warmup", "1")

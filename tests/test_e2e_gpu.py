@@ -1273,6 +1273,64 @@ def test_bench_under_torch_distributed_run_one_rank(tmp_path):
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0 and d["scaling"] == "weak"
 
 
+def test_bench_plain_run_dumps_its_outputs_and_full_adds_the_extras(tmp_path):
+    """A plain `bench.py --steps K` times the headline only (no roofline / cpu_baseline / also) and --dump-outputs writes what one step from
+    the seeded start computed as float32 .npy; --full adds the measurements beside the headline (here the roofline alone).  One fp32 step from the seeded
+    weights is held to the CPU oracle on the same seeded batch (losses, pose), and its parameters must be the ones after the optimizer step."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    import json
+    import subprocess
+    import sys
+
+    from gdrnet_amd import GDRN
+    from gdrnet_amd.engine import LOSS_NAMES
+    from oracle import gdrn_oracle as O
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(*extra):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--bs", "8", *extra]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+
+    names = ("losses", "rot", "trans", "params", "bn_running_stats")
+    d = run("--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / "out"))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "bf16"
+    assert not {"roofline", "cpu_baseline", "also", "parity", "fp32_parity_mode"} & set(d)
+    o = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in names}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in o.values())
+    assert o["losses"].shape == (8,) and o["rot"].shape == (8, 3, 3) and o["trans"].shape == (8, 3) and o["params"].shape == (1 << 22,)
+    assert sum(a.nbytes for a in o.values()) <= 64 << 20
+    # the same arguments again: the same inputs, the same outputs up to the last bits of the fp32-atomic weight-gradient sums
+    run("--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / "again"))
+    for k, a in o.items():
+        np.testing.assert_allclose(np.load(tmp_path / "again" / f"{k}.npy"), a, rtol=1e-5, atol=1e-7, err_msg=k)
+
+    # fp32: the dumped losses / pose are those of the seeded weights on the seeded batch (bench: weights seed 0, batch seed 1), the dumped
+    # parameters the seeded ones moved by the optimizer step
+    run("--dtype", "fp32", "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "one"))
+    one = {k: np.load(tmp_path / "one" / f"{k}.npy") for k in names}
+    sd = synth.make_state_dict(0)
+    with torch.no_grad():
+        ref = O.gdrn_forward(sd, synth.make_batch(8, seed=1), do_loss=True, training=True, bufs={})
+    for i, k in enumerate(LOSS_NAMES):
+        v = ref["loss_dict"][k].item()
+        assert abs(one["losses"][i] - v) / max(abs(v), 1e-3) < 1e-3, (k, one["losses"][i], v)
+    for k in ("rot", "trans"):
+        assert np.linalg.norm(one[k] - ref[k].numpy()) / np.linalg.norm(ref[k].numpy()) < 1e-3, k
+    m, _ = GDRN.build_model_optimizer(lm13_cfg(device="cpu"))
+    m.load_state_dict(sd)
+    p0 = torch.cat([p.detach().reshape(-1) for _, p in m.named_parameters()]).numpy()
+    p0 = p0[np.sort(np.random.default_rng(0).choice(p0.size, 1 << 22, replace=False))]
+    delta = np.abs(one["params"] - p0)
+    assert (delta > 0).mean() > 0.5 and delta.max() < 0.1, ((delta > 0).mean(), delta.max())
+
+    d = run("--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extras")
+    assert d["roofline"]["launches_per_step"] > 0 and "cpu_baseline" not in d
+
+
 def test_training_on_one_batch_reduces_the_loss_in_both_precisions():
     """End-to-end optimisation sanity beyond one-step gradient parity: 120 fused steps (forward + 8 losses + backward + Ranger at the
     config's rate) on ONE synthetic batch must drive the total loss down, in the bf16 throughput mode as in the fp32 parity mode, along
