@@ -136,7 +136,7 @@ def to_device_table(structs, device):
     return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
 
 
-# name -> argtypes (all return int status, except the two tile queries which return ints too)
+# name -> argtypes (all return int status, except the two tile queries which return ints too, and the byte counts of _RET_LL: long long)
 _SIGS = {
     "gdrn_version": [],
     "gdrn_last_hip_error": [C.c_char_p, I],
@@ -233,9 +233,13 @@ _SIGS = {
     "gdrn_roi_affine": [P, I, I, I, P, P, P, P, P],
     "gdrn_roi_crop_inputs": [P, P, I, I, I, C.POINTER(D), C.POINTER(D), P, P, P],
     "gdrn_roi_targets": [P, P, I, I, P, I, P, P, P, P, P, P, P],
+    "gdrn_pose_metrics_workspace_bytes": [I, I],
+    "gdrn_pose_errors": [P, P, P, P, P, P, P, I, P, P, I, P, P, P, I, I, P, P, P],
+    "gdrn_pose_recall_accumulate": [P, P, P, I, P, I, P, P, P, P, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []
+_RET_LL = ("gdrn_workspace_bytes", "gdrn_pose_metrics_workspace_bytes")
 EXPORTS = tuple(_SIGS.keys())
 _libs = {}
 
@@ -266,7 +270,7 @@ def load(dtype=BF16):
     for name, args in _SIGS.items():
         fn = getattr(lib, name)
         fn.argtypes = args
-        fn.restype = LL if name == "gdrn_workspace_bytes" else I
+        fn.restype = LL if name in _RET_LL else I
     if lib.gdrn_half_format() != kind:
         raise GdrnHipError(f"{path} computes 16-bit dtype code {lib.gdrn_half_format()}, expected {kind}")
     _libs[kind] = lib

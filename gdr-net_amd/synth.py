@@ -350,3 +350,63 @@ def make_region_inputs(B=4, res=64, nfps=64):
     if B > 2:
         xyz[2] = 0
     return dict(xyz=xyz, fps_points=fps)
+
+
+POSE_METRIC_SEEDS = {"A": 91, "B": 92}   # the seeds golden G12 was drawn with (tests/golden/make_golden_g12.py moves on if a draw sits on a threshold)
+
+
+def _axis_angle(axis, deg):
+    """[n,3,3] fp64 rotations about unit `axis` [n,3] by `deg` [n] degrees (Rodrigues)."""
+    a = np.deg2rad(deg)[:, None, None]
+    x, y, z = axis[:, 0], axis[:, 1], axis[:, 2]
+    o = np.zeros_like(x)
+    Kx = np.stack([o, -z, y, z, o, -x, -y, x, o], axis=1).reshape(-1, 3, 3)
+    return np.eye(3)[None] + np.sin(a) * Kx + (1.0 - np.cos(a)) * (Kx @ Kx)
+
+
+def make_pose_metric_inputs(case="A", seed=None):
+    """Inputs of the pose-error golden G12 (gdrnet_amd.pose_metrics against lib/pysixd/pose_error.py and the evaluator's recall table), fp64.
+
+    case "A": 67 rows cycling through three classes -- 0: 1031 points, non-symmetric; 1: 257 points, symmetric under pi about z and pi about x;
+    2: ONE point, symmetric, its single symmetry handed over as a bare 3x3 -- estimates = a rotation of 0.1 .. 20 degrees times the ground truth (times
+    one of the class's symmetries on every fourth row of a symmetric class), translation offsets of 0 .. 0.15 m, rows 0 and 4 with the estimate equal
+    to the ground truth, rows 7 and 10 (class 1) with R_est = R_gt S_k exactly, and 8 ground-truth instances without a prediction.
+    case "B": 3 rows of one symmetric class of 8195 points (one more than a power of two: ragged last slab and last tile)."""
+    seed = POSE_METRIC_SEEDS[case] if seed is None else seed
+    u = lambda tag, *shape: hash_uniform(seed, tag, shape)  # noqa: E731
+    rz, rx = np.diag([-1.0, -1.0, 1.0]), np.diag([1.0, -1.0, -1.0])
+    if case == "A":
+        N, sizes, diam = 67, (1031, 257, 1), [0.2, 0.3, 0.1]
+        sym_infos, sym_classes, names = [None, np.stack([rz, rx]), rz.copy()], (1, 2), ["driller", "ape", "cat"]
+        missing = {0: 3, 1: 3, 2: 2}
+    elif case == "B":
+        N, sizes, diam = 3, (8195,), [0.25]
+        sym_infos, sym_classes, names = [rz[None].copy()], (0,), ["eggbox"]
+        missing = {}
+    else:
+        raise ValueError(case)
+    points = [-0.1 + 0.2 * u(f"pts{c}", n, 3) for c, n in enumerate(sizes)]
+    labels = np.arange(N, dtype=np.int64) % len(sizes)
+    R_gt = _random_rotations(seed, "R_gt", N)
+    t_gt = np.concatenate([0.3 * u("t_xy", N, 2) - 0.15, 0.6 + 0.8 * u("t_z", N, 1)], axis=1)
+    q = u("quality", N)
+    ang = 0.1 * 200.0 ** (0.7 * q + 0.3 * u("q_ang", N))
+    off = 0.15 * (0.7 * q + 0.3 * u("q_off", N)) ** 2
+    axis = hash_normal(seed, "axis", (N, 3))
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    tdir = hash_normal(seed, "tdir", (N, 3))
+    tdir /= np.linalg.norm(tdir, axis=1, keepdims=True)
+    R_est = _axis_angle(axis, ang) @ R_gt
+    t_est = t_gt + off[:, None] * tdir
+    for i in range(N):
+        s = sym_infos[labels[i]]
+        if s is not None and (i // len(sizes)) % 4 == 3:
+            s = s.reshape(-1, 3, 3)
+            R_est[i] = R_est[i] @ s[(i // (4 * len(sizes))) % len(s)]
+    if case == "A":
+        for i in (0, 4):
+            R_est[i], t_est[i] = R_gt[i], t_gt[i]
+        R_est[7], R_est[10] = R_gt[7] @ sym_infos[1][0], R_gt[10] @ sym_infos[1][1]
+    K = np.repeat(LM_K.astype(np.float64)[None], N, axis=0)
+    return dict(points=points, diameters=np.array(diam), sym_infos=sym_infos, sym_classes=sym_classes, obj_names=names, labels=labels,
+                R_est=R_est, t_est=t_est, R_gt=R_gt, t_gt=t_gt, K=K, missing=missing, seed=seed)

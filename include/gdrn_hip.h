@@ -690,6 +690,33 @@ int gdrn_roi_targets(const gdrn_roi_task* tasks_dev, const double* minv, int B, 
                      const float* extents, float* roi_xyz, float* roi_mask_trunc, float* roi_mask_visib, float* roi_mask_obj,
                      int* roi_region, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pose-error metrics and recall table on the device (added within ABI 5: new entry points, nothing changed): what the reference's
+ * evaluator computes on the host per instance right after inference (GDRN_EvaluatorCustom._eval_predictions,
+ * core/gdrn_modeling/gdrn_custom_evaluator.py:493-670 with lib/pysixd/pose_error.py:297-444 and get_closest_rot, core/utils/pose_utils.py:430-454).
+ * All arithmetic and every output is fp64, like the reference's numpy.  Per row i of N:
+ *   R_est, R_gt [N][3][3], t_est, t_gt [N][3], K [N][3][3] fp64;  labels [N] int32 (class of the row) on the device, labels_host the same N
+ *   values in host memory: they are checked against [0, C) on the host before anything is launched (GDRN_ERR_ARG).
+ * Per-class tables (device): pts [C][n_max][3] fp64 with npts [C] valid rows each (the padding is never read into a sum or a minimum),
+ *   is_sym [C] int32 (non-zero: the class is scored with adi and the closest-rotation search), sym [C][Kmax][3][3] fp64 with nsym [C] valid
+ *   entries each (Kmax = 0: sym / nsym may be NULL).
+ * err [N][4] = (ad, re, te, proj):  te = |t_gt - t_est|;  R_gt' = R_gt, replaced by R_gt S_k for each symmetry of a symmetric class, in table
+ *   order, whenever re(R_est, R_gt S_k) is strictly smaller;  re = re(R_est, R_gt') in degrees;  proj = mean reprojection distance of the class's
+ *   points under (R_est, t_est) and (R_gt', t_gt), pixels;  ad = add (mean distance of corresponding points) for a non-symmetric class, adi
+ *   (mean distance from each ground-truth-posed point to the nearest estimate-posed point, exact, with the plain R_gt) for a symmetric one.
+ * workspace: gdrn_pose_metrics_workspace_bytes(N, n_max) bytes of device memory, no initialisation needed.  Sums are reduced in a fixed order
+ *   (no floating-point atomics): the same call gives the same bits. */
+long long gdrn_pose_metrics_workspace_bytes(int N, int n_max);
+int gdrn_pose_errors(const double* R_est, const double* t_est, const double* R_gt, const double* t_gt, const double* K, const int* labels,
+                     const int* labels_host, int N, const double* pts, const int* npts, int n_max, const int* is_sym, const double* sym,
+                     const int* nsym, int Kmax, int C, double* err, void* workspace, void* stream);
+/* Adds the rows of err [N][4] to the caller's per-class running state (device memory, zeroed by the caller before the first call):
+ * hits [C][15] = counts of ad < {0.02, 0.05, 0.10} diameter | (re < d and te < d/100), d = 2, 5, 10 | re < {2, 5, 10} | te < {0.02, 0.05, 0.10} |
+ * proj < {2, 5, 10} (strict, the order of the evaluator's metric_names);  seen [C] and err_cnt [C] += rows of the class;  re_sum / te_sum [C] +=
+ * their re / te (one workgroup per class, fixed order).  diameter [C] fp64.  Calls on one stream follow each other. */
+int gdrn_pose_recall_accumulate(const double* err, const int* labels, const int* labels_host, int N, const double* diameter, int C,
+                                long long* hits, long long* seen, double* re_sum, double* te_sum, long long* err_cnt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
