@@ -236,10 +236,15 @@ _SIGS = {
     "gdrn_pose_metrics_workspace_bytes": [I, I],
     "gdrn_pose_errors": [P, P, P, P, P, P, P, I, P, P, I, P, P, P, I, I, P, P, P],
     "gdrn_pose_recall_accumulate": [P, P, P, I, P, I, P, P, P, P, P, P],
+    "gdrn_pnp_workspace_bytes": [I, I, I],
+    "gdrn_pnp_ransac": [P, P, P, P, P, I, I, D, I, C.c_ulonglong, I, P, P, P, P, P, P, P, P],
+    "gdrn_pnp_refine": [P, P, P, P, P, I, I, I, P, P, P, P, P, P],
+    "gdrn_pnp_ransac_f64": [P, P, P, P, P, I, I, D, I, C.c_ulonglong, I, P, P, P, P, P, P, P, P],
+    "gdrn_pnp_refine_f64": [P, P, P, P, P, I, I, I, P, P, P, P, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []
-_RET_LL = ("gdrn_workspace_bytes", "gdrn_pose_metrics_workspace_bytes")
+_RET_LL = ("gdrn_workspace_bytes", "gdrn_pose_metrics_workspace_bytes", "gdrn_pnp_workspace_bytes")
 EXPORTS = tuple(_SIGS.keys())
 _libs = {}
 

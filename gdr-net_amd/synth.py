@@ -410,3 +410,52 @@ def make_pose_metric_inputs(case="A", seed=None):
     K = np.repeat(LM_K.astype(np.float64)[None], N, axis=0)
     return dict(points=points, diameters=np.array(diam), sym_infos=sym_infos, sym_classes=sym_classes, obj_names=names, labels=labels,
                 R_est=R_est, t_est=t_est, R_gt=R_gt, t_gt=t_gt, K=K, missing=missing, seed=seed)
+
+
+PNP_COUNTS = (0, 3, 4, 5, 257, 1025, 4096, 600)   # empty | below minimal | minimal | clean | one past a workgroup stride | one past a scoring tile | full map | coplanar
+PNP_SEEDS = {"clean": 131, "noisy": 132}
+
+
+def make_pnp_inputs(case="clean", seed=None, stride=4096):
+    """Inputs of the PnP tests (gdrnet_amd.pnp), fp64: N = 8 RoIs with PNP_COUNTS valid correspondences each in arrays of `stride` rows whose
+    padding is NaN; model points in a 0.1 m box (RoI 7: all in one plane), per-RoI K near the LM camera, t_z from 0.3 to 2 m, rotations that
+    include the identity (RoI 3) and one 5e-4 rad short of pi (RoI 5).  The RoIs with >= 257 points carry 40 % outliers displaced by 20 .. 80 px;
+    the others are outlier-free.  case "clean": the inliers' image points are the exact projections; "noisy": displaced uniformly within a 1 px disc.
+    Returns image_points [8,S,2], model_points [8,S,3], counts [8] int32, K [8,3,3], R [8,3,3], t [8,3], inlier [8,S] bool (the true inlier set)."""
+    seed = PNP_SEEDS[case] if seed is None else seed
+    u = lambda tag, *shape: hash_uniform(seed, tag, shape)  # noqa: E731
+    N = len(PNP_COUNTS)
+    R = _random_rotations(seed, "R", N)
+    R[3] = np.eye(3)
+    axis = hash_normal(seed, "axis", (1, 3))
+    R[5] = _axis_angle(axis / np.linalg.norm(axis), np.rad2deg(np.array([np.pi - 5e-4])))[0]
+    tz = np.array([1.0, 0.7, 0.3, 0.5, 0.8, 1.3, 2.0, 0.6])
+    t = np.concatenate([(0.3 * u("t_xy", N, 2) - 0.15) * tz[:, None], tz[:, None]], axis=1)
+    K = np.repeat(LM_K.astype(np.float64)[None], N, axis=0)
+    K[:, 0, 0] += 4.0 * (u("fx", N) - 0.5)
+    K[:, 1, 1] += 4.0 * (u("fy", N) - 0.5)
+    K[:, :2, 2] += 6.0 * (u("c", N, 2) - 0.5)
+    img = np.full((N, stride, 2), np.nan)
+    mod = np.full((N, stride, 3), np.nan)
+    inl = np.zeros((N, stride), dtype=bool)
+    for n, c in enumerate(PNP_COUNTS):
+        if c == 0:
+            continue
+        X = 0.1 * u(f"X{n}", c, 3) - 0.05
+        if n == 7:
+            X[:, 2] = 0.3 * X[:, 0] - 0.2 * X[:, 1] + 0.01   # one plane, not through the origin
+        p = (X @ R[n].T + t[n]) @ K[n].T
+        uv = p[:, :2] / p[:, 2:3]
+        good = np.ones(c, dtype=bool)
+        if c >= 257:
+            good = u(f"out{n}", c) >= 0.4
+            good[:4] = True
+        ang, rad = 2.0 * math.pi * u(f"dir{n}", c), u(f"rad{n}", c)
+        d = np.stack([np.cos(ang), np.sin(ang)], axis=1)
+        if case == "noisy":
+            uv = uv + np.where(good[:, None], np.sqrt(rad)[:, None] * d, 0.0)
+        elif case != "clean":
+            raise ValueError(case)
+        uv = uv + np.where(good[:, None], 0.0, (20.0 + 60.0 * rad)[:, None] * d)
+        img[n, :c], mod[n, :c], inl[n, :c] = uv, X, good
+    return dict(image_points=img, model_points=mod, counts=np.array(PNP_COUNTS, dtype=np.int32), K=K, R=R, t=t, inlier=inl, seed=seed)

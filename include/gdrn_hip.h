@@ -717,6 +717,44 @@ int gdrn_pose_errors(const double* R_est, const double* t_est, const double* R_g
 int gdrn_pose_recall_accumulate(const double* err, const int* labels, const int* labels_host, int N, const double* diameter, int C,
                                 long long* hits, long long* seen, double* re_sum, double* te_sum, long long* err_cnt, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Batched PnP-RANSAC and iterative PnP (added within ABI 5: new entry points, nothing changed): the step the reference's evaluator runs per RoI
+ * on the host with cv2.solvePnPRansac / cv2.solvePnP between the correspondences and the pose metrics --
+ *   GDRN_Evaluator.process_pnp_ransac (core/gdrn_modeling/gdrn_evaluator.py:316-392 -> lib/pysixd/misc.py:145-194) and process_net_and_pnp
+ *   (:187-307), i.e. cfg.TEST.PNP_TYPE = ransac_pnp | net_ransac_pnp | net_iter_pnp --
+ * for a whole batch, one workgroup per RoI.  Inputs are what gdrn_correspondences writes:
+ *   img_pts [N][stride][2] pixels, model_pts [N][stride][3], fp32 (the *_f64 twins: the same layout in fp64, as cv2 accepts either);
+ *   counts [N] int32 on the device: only the first counts[n] rows of RoI n are valid, the rest is never read into a result;  counts_host: the same
+ *   N values in host memory, checked against [0, stride] before anything is launched (GDRN_ERR_ARG);  K [N][3][3] fp64.
+ * All pose arithmetic is fp64.  R [N][3][3], t [N][3] fp64 are in/out: a RoI that cannot be solved (counts[n] < 4, no hypothesis with >= 4 inliers, a
+ * non-finite result) keeps the caller's values and gets ok[n] = 0 (num_inliers 0, inlier_mask 0, rms NaN), every other one ok[n] = 1.
+ * gdrn_pnp_ransac.  Sampling: hypothesis h of RoI n takes draws d = 0, 1, ... of
+ *     x = mix64(seed * 0x9E3779B97F4A7C15 + n * 0xBF58476D1CE4E5B9 + h * 0x94D049BB133111EB + d * 0xD6E8FEB86659FD93)   (mod 2^64; mix64 = the
+ *     splitmix64 finaliser),  index = ((x >> 32) * counts[n]) >> 32,
+ *   keeping the first 4 distinct indices (a collision advances d; after 64 draws the hypothesis is dropped): no RNG state, the same (seed, inputs)
+ *   give the same samples whatever the launch shape.  Minimal solve: P3P on the first three samples after normalising with K^-1, the solution with the
+ *   smallest reprojection error on the fourth; a degenerate sample scores 0.  Scoring: inliers are the points with z > 0 and a squared pixel
+ *   error < reproj_err^2, counted as integers.  Selection: the highest count wins, ties go to the lowest h.  The winner is refined on its inliers
+ *   (below), the inliers are re-selected under the refined pose, and it is refined once more: inlier_mask [N][stride] u8 (or NULL), num_inliers [N]
+ *   and rms [N] (or NULL; root of the inliers' mean squared pixel distance) are those of the returned pose.
+ * Refinement (both calls): minimises the sum of squared pixel distances by Levenberg-Marquardt on (rotation-vector increment applied on the left,
+ *   translation increment); stop rule: a step below 1e-10 (rotation in rad, translation relative to |t|) is applied and ends it, as do max_iter
+ *   evaluations (the reference's default solver has 20).  Sums are reduced in a fixed order, no floating-point atomics: repeated calls are bit-identical.
+ * gdrn_pnp_refine: from the caller's (R, t) over all counts[n] points without a gate (SOLVEPNP_ITERATIVE with useExtrinsicGuess); rms over all of them.
+ * workspace: gdrn_pnp_workspace_bytes(N, stride, iters) bytes of device memory, no initialisation needed (gdrn_pnp_refine uses none: may be NULL).
+ * Not cv2's algorithm: a fixed hypothesis count instead of the 0.99-confidence early stop, P3P + least squares instead of EPnP. */
+long long gdrn_pnp_workspace_bytes(int N, int stride, int iters);
+int gdrn_pnp_ransac(const float* img_pts, const float* model_pts, const int* counts, const int* counts_host, const double* K, int N, int stride,
+                    double reproj_err, int iters, unsigned long long seed, int max_iter, double* R, double* t, int* ok, int* num_inliers,
+                    unsigned char* inlier_mask, double* rms, void* workspace, void* stream);
+int gdrn_pnp_refine(const float* img_pts, const float* model_pts, const int* counts, const int* counts_host, const double* K, int N, int stride,
+                    int max_iter, double* R, double* t, int* ok, double* rms, void* workspace, void* stream);
+int gdrn_pnp_ransac_f64(const double* img_pts, const double* model_pts, const int* counts, const int* counts_host, const double* K, int N,
+                        int stride, double reproj_err, int iters, unsigned long long seed, int max_iter, double* R, double* t, int* ok,
+                        int* num_inliers, unsigned char* inlier_mask, double* rms, void* workspace, void* stream);
+int gdrn_pnp_refine_f64(const double* img_pts, const double* model_pts, const int* counts, const int* counts_host, const double* K, int N,
+                        int stride, int max_iter, double* R, double* t, int* ok, double* rms, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
