@@ -241,6 +241,8 @@ _SIGS = {
     "gdrn_pnp_refine": [P, P, P, P, P, I, I, I, P, P, P, P, P, P],
     "gdrn_pnp_ransac_f64": [P, P, P, P, P, I, I, D, I, C.c_ulonglong, I, P, P, P, P, P, P, P, P],
     "gdrn_pnp_refine_f64": [P, P, P, P, P, I, I, I, P, P, P, P, P, P],
+    "gdrn_render_depth": [P, P, P, P, P, P, I, I, P, P, P, P, P, I, I, I, D, D, P, P],
+    "gdrn_xyz_from_depth": [P, P, P, P, I, I, I, P, P, P, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []

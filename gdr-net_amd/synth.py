@@ -459,3 +459,119 @@ def make_pnp_inputs(case="clean", seed=None, stride=4096):
         uv = uv + np.where(good[:, None], 0.0, (20.0 + 60.0 * rad)[:, None] * d)
         img[n, :c], mod[n, :c], inl[n, :c] = uv, X, good
     return dict(image_points=img, model_points=mod, counts=np.array(PNP_COUNTS, dtype=np.int32), K=K, R=R, t=t, inlier=inl, seed=seed)
+
+
+# ----------------------------------------------------------------------------------------------
+# meshes and scenes of the depth rasterizer (gdrnet_amd.render, golden G13)
+# ----------------------------------------------------------------------------------------------
+def mesh_cube(edge=1.0):
+    """axis-aligned cube centred on the origin: ([8,3] fp64 vertices, [12,3] int32 faces)."""
+    v = np.array([[x, y, z] for z in (-0.5, 0.5) for y in (-0.5, 0.5) for x in (-0.5, 0.5)], dtype=np.float64) * float(edge)
+    f = np.array([[0, 1, 3], [0, 3, 2], [4, 7, 5], [4, 6, 7], [0, 5, 1], [0, 4, 5], [2, 3, 7], [2, 7, 6], [0, 2, 6], [0, 6, 4], [1, 5, 7], [1, 7, 3]],
+                 dtype=np.int32)
+    return v, f
+
+
+def mesh_rectangle(nx, ny, xs=None, ys=None):
+    """the rectangle [xs[0], xs[-1]] x [ys[0], ys[-1]] in the plane z = 0 as nx x ny cells of two triangles each (the diagonal from a cell's
+    low corner): ([(nx+1)(ny+1),3] fp64 vertices, [2 nx ny,3] int32 faces).  xs / ys: the nx+1 / ny+1 grid coordinates (default: uniform on
+    [-0.5, 0.5])."""
+    xs = np.linspace(-0.5, 0.5, nx + 1) if xs is None else np.asarray(xs, dtype=np.float64)
+    ys = np.linspace(-0.5, 0.5, ny + 1) if ys is None else np.asarray(ys, dtype=np.float64)
+    assert xs.shape == (nx + 1,) and ys.shape == (ny + 1,)
+    gx, gy = np.meshgrid(xs, ys)
+    v = np.stack([gx.ravel(), gy.ravel(), np.zeros(gx.size)], axis=1)
+    j, i = np.meshgrid(np.arange(nx), np.arange(ny))
+    p = (i * (nx + 1) + j).ravel()
+    f = np.concatenate([np.stack([p, p + 1, p + nx + 2], axis=1), np.stack([p, p + nx + 2, p + nx + 1], axis=1)], axis=0).astype(np.int32)
+    return v, f
+
+
+def mesh_icosphere(subdivisions, radius=1.0, perturb=0.0, seed=0):
+    """icosahedron subdivided `subdivisions` times (20 * 4^s faces) on the sphere of `radius`; perturb > 0 scales every vertex radially by
+    1 + perturb * (u - 0.5), u hashed per vertex: a non-convex, self-occluding closed surface."""
+    g = (1.0 + math.sqrt(5.0)) / 2.0
+    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    v = [np.array(p, dtype=np.float64) / math.sqrt(1.0 + g * g) for p in v]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(subdivisions):
+        mid, nf = {}, []
+
+        def midpoint(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                m = v[a] + v[b]
+                v.append(m / np.linalg.norm(m))
+                mid[key] = len(v) - 1
+            return mid[key]
+
+        for a, b, c in f:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    v = np.stack(v)
+    scale = radius * (1.0 + perturb * (hash_uniform(seed, "icosphere/r", (len(v),)) - 0.5)) if perturb else np.full(len(v), float(radius))
+    return v * scale[:, None], np.array(f, dtype=np.int32)
+
+
+RENDER_SEEDS = {"cube": 141, "watertight": 142, "sphere": 143, "mixed": 144, "clip": 145}
+# ^ the seeds golden G13 was drawn with (tests/golden/make_golden_g13.py moves on while a pixel centre sits within 1e-6 px of an edge)
+
+
+def make_render_inputs(case, seed=None):
+    """Scenes of the depth rasterizer, fp64: dict(vertices, faces (lists, one entry per class), labels, R, t, K (per instance), H, W, near, far, seed).
+
+    "cube"        one 0.1 m cube, 4 random poses, 48 x 64, K with a skew term
+    "watertight"  a fronto-parallel rectangle at z = 2 of 32 x 32 cells whose vertices project exactly onto the integer pixels 0, 2, .., 62, 63 of a
+                  64 x 64 frame (power-of-two focal length: every quantity of the rasterizer is exact): every pixel centre lies on an edge or a vertex
+    "sphere"      the perturbed icosphere (subdivision 3, 1280 faces), one pose, 96 x 128
+    "mixed"       3 classes of 12 / 2048 / 1280 faces (cube, rectangle of 32 x 32 cells, perturbed icosphere), labels [2, 0, 1, 1, 0], 120 x 160
+    "clip"        48 x 64: a cube half outside the frame | entirely outside | behind the camera | a strip along the viewing direction whose first
+                  cell crosses the near plane | a cube beyond far"""
+    seed = RENDER_SEEDS[case] if seed is None else seed
+    u = lambda tag, *shape: hash_uniform(seed, tag, shape)  # noqa: E731
+    near, far = 0.01, 6.5
+    if case == "cube":
+        H, W, N = 48, 64, 4
+        meshes, labels = [mesh_cube(0.1)], np.zeros(N, dtype=np.int64)
+        K = np.array([[70.0, 0.3, 31.7], [0.0, 71.0, 23.4], [0.0, 0.0, 1.0]])
+        R = _random_rotations(seed, "R", N)
+        t = np.concatenate([0.08 * u("t_xy", N, 2) - 0.04, 0.3 + 0.2 * u("t_z", N, 1)], axis=1)
+    elif case == "watertight":
+        H, W, N = 64, 64, 1
+        px = np.concatenate([np.arange(0, 63, 2), [63]]).astype(np.float64)   # 33 grid lines: pixels 0, 2, .., 62, 63
+        K = np.array([[32.0, 0.0, 8.0], [0.0, 32.0, 8.0], [0.0, 0.0, 1.0]])
+        meshes, labels = [mesh_rectangle(32, 32, xs=2.0 * (px - 8.0) / 32.0, ys=2.0 * (px - 8.0) / 32.0)], np.zeros(N, dtype=np.int64)
+        R, t = np.eye(3)[None].copy(), np.array([[0.0, 0.0, 2.0]])
+    elif case == "sphere":
+        H, W, N = 96, 128, 1
+        meshes, labels = [mesh_icosphere(3, 0.06, 0.35, seed)], np.zeros(N, dtype=np.int64)
+        K = np.array([[143.1, 0.0, 63.2], [0.0, 143.4, 47.6], [0.0, 0.0, 1.0]])
+        R = _random_rotations(seed, "R", N)
+        t = np.concatenate([0.04 * u("t_xy", N, 2) - 0.02, 0.3 + 0.1 * u("t_z", N, 1)], axis=1)
+    elif case == "mixed":
+        H, W, N = 120, 160, 5
+        rv, rf = mesh_rectangle(32, 32)
+        meshes = [mesh_cube(0.08), (rv * np.array([0.12, 0.09, 1.0]), rf), mesh_icosphere(3, 0.05, 0.35, seed)]
+        labels = np.array([2, 0, 1, 1, 0], dtype=np.int64)
+        K = LM_K.astype(np.float64) / 4.0
+        K[2, 2] = 1.0
+        R = _random_rotations(seed, "R", N)
+        t = np.concatenate([0.2 * u("t_xy", N, 2) - 0.1, 0.4 + 0.3 * u("t_z", N, 1)], axis=1)
+    elif case == "clip":
+        H, W, N = 48, 64, 5
+        sv, sf = mesh_rectangle(1, 4)
+        meshes = [mesh_cube(0.1), (sv * np.array([0.05, 0.4, 1.0]), sf)]
+        labels = np.array([0, 0, 0, 1, 0], dtype=np.int64)
+        K = np.array([[70.0, 0.0, 31.7], [0.0, 71.0, 23.4], [0.0, 0.0, 1.0]])
+        R = _random_rotations(seed, "R", N)
+        t = np.array([[0.0, 0.0, 0.4], [0.9, 0.0, 0.4], [0.0, 0.0, -0.5], [0.0, 0.03, 0.2], [0.0, 0.0, 7.0]]) + 0.004 * (u("t_jit", N, 3) - 0.5)
+        t[0, 0] = (W - 1 - K[0, 2]) / K[0, 0] * t[0, 2]   # the cube's centre projects onto the last pixel column
+        # the strip: model y runs along the camera's z (from ~0 to ~0.4 m), tilted by about a degree so that no edge is axis-parallel
+        axis = hash_normal(seed, "tilt_axis", (1, 3))
+        R[3] = _axis_angle(axis / np.linalg.norm(axis), np.array([1.0]))[0] @ np.array([[1.0, 0.0, 0.0], [0.0, 0.0, -1.0], [0.0, 1.0, 0.0]])
+    else:
+        raise ValueError(case)
+    return dict(vertices=[m[0] for m in meshes], faces=[m[1] for m in meshes], labels=labels, R=R, t=t, K=np.repeat(K[None], N, axis=0),
+                H=H, W=W, near=near, far=far, seed=seed)

@@ -755,6 +755,40 @@ int gdrn_pnp_ransac_f64(const double* img_pts, const double* model_pts, const in
 int gdrn_pnp_refine_f64(const double* img_pts, const double* model_pts, const int* counts, const int* counts_host, const double* K, int N,
                         int stride, int max_iter, double* R, double* t, int* ok, double* rms, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Batched depth rasterizer and object-coordinate targets (added within ABI 5: new entry points, nothing changed): what the reference makes in an
+ * offline pass per annotated instance (tools/lm/lm_pbr_1_gen_xyz_crop.py) -- an OpenGL depth render of the object under the ground-truth pose,
+ * misc.calc_xyz_bp_fast (lib/pysixd/misc.py:288-316) and mask2bbox_xyxy (lib/utils/mask_utils.py:39-44) -- for N instances per call.
+ * Mesh table (device, packed without padding): verts [sum nverts][3] fp64 metres and faces [sum nfaces][3] int32 (vertex indices within the class),
+ *   class c owning the rows vert_off[c] .. + nverts[c] and face_off[c] .. + nfaces[c];  f_max = the largest nfaces[c] (sizes the launch).
+ * Per instance i: labels[i] (device int32; labels_host the same N values in host memory, checked against [0, C) before anything is launched),
+ *   R [N][3][3], t [N][3] (model -> camera, metres), K [N][3][3] fp64: upper triangular, read as [[fx, s, cx], [0, fy, cy], [0, 0, 1]].
+ * gdrn_render_depth: depth [N][H][W] fp32 = camera-space z in metres of the nearest surface, 0 where nothing is drawn.  The rules:
+ *   rays       pixel (x, y), integer coordinates, is sampled on d = K^-1 [x, y, 1] -- the ray calc_xyz_bp_fast back-projects along; no half-pixel offset
+ *   coverage   with camera-space vertices a, b, c: covered when d.(a x b), d.(b x c), d.(c x a) are all >= 0 or all <= 0 (ray space, no perspective
+ *              divide; edges inclusive, both windings, no culling)
+ *   depth      z = (n.a) / (n.d), n = (b - a) x (c - a): exact under perspective
+ *   precision  setup and per-pixel arithmetic in fp64, the depth rounded to fp32 once
+ *   order      a face's vertex indices are sorted ascending first and every edge's cross product is taken on its vertex pair in ascending index
+ *              order: two triangles evaluate the same bits for a shared edge, so a pixel exactly on it is never dropped by both (watertight), and
+ *              the result depends neither on the order of the faces nor on their winding
+ *   depth test the nearest fragment wins by an unsigned atomic min on the bits of the positive fp32 depth; the buffer is cleared to +inf and
+ *              resolved to 0 inside the call: independent of scheduling, repeated calls are bit-identical
+ *   dropped    a triangle with any vertex at z < near, WHOLE -- there is NO near-plane clipping (BOP objects are in front of the camera);  a
+ *              degenerate triangle (n == 0);  a fragment with n.d == 0, with z > far, or whose fp32 depth is not positive and finite
+ *   frame      a triangle's pixel walk is clipped to the frame; an instance entirely outside leaves its slice all zero
+ *   0 < near < far is required (the tool's values: 0.01, 6.5).
+ * gdrn_xyz_from_depth: depth [N][H][W] fp32 from the call above or from the caller;  xyz [N][H][W][3] fp32 = R^T (depth K^-1 [x, y, 1] - t)
+ *   evaluated in fp64, exactly 0 where depth == 0;  mask [N][H][W] u8 = depth != 0;  xyxy [N][4] int32 = the inclusive bounds of the mask
+ *   (x1, y1, x2, y2; integer atomic min / max, finished on the device);  visible [N] int32 = the mask is not empty.  An empty mask gives
+ *   xyxy = (0, 0, W - 1, H - 1), visible = 0 and an all-zero xyz, the tool's record of an instance that is not visible (:142-150).
+ * Neither call needs scratch memory or reads anything back. */
+int gdrn_render_depth(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off, const int* nfaces,
+                      int C, int f_max, const int* labels, const int* labels_host, const double* R, const double* t, const double* K, int N,
+                      int H, int W, double near, double far, float* depth, void* stream);
+int gdrn_xyz_from_depth(const float* depth, const double* R, const double* t, const double* K, int N, int H, int W, float* xyz,
+                        unsigned char* mask, int* xyxy, int* visible, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
