@@ -243,10 +243,16 @@ _SIGS = {
     "gdrn_pnp_refine_f64": [P, P, P, P, P, I, I, I, P, P, P, P, P, P],
     "gdrn_render_depth": [P, P, P, P, P, P, I, I, P, P, P, P, P, I, I, I, D, D, P, P],
     "gdrn_xyz_from_depth": [P, P, P, P, I, I, I, P, P, P, P, P],
+    "gdrn_vsd_workspace_bytes": [I, I, I, I],
+    "gdrn_vsd": [P, P, P, P, P, I, P, P, I, I, I, D, P, I, I, I, P, P, P, P],
+    "gdrn_mssd_mspd_workspace_bytes": [I, I, I],
+    "gdrn_mssd_mspd": [P, P, P, P, P, P, P, I, P, P, I, P, P, P, I, I, P, P, P],
+    "gdrn_bop_recall_accumulate": [P, I, P, P, P, I, P, I, D, P, P, P, P, P, P, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []
-_RET_LL = ("gdrn_workspace_bytes", "gdrn_pose_metrics_workspace_bytes", "gdrn_pnp_workspace_bytes")
+_RET_LL = ("gdrn_workspace_bytes", "gdrn_pose_metrics_workspace_bytes", "gdrn_pnp_workspace_bytes", "gdrn_vsd_workspace_bytes",
+           "gdrn_mssd_mspd_workspace_bytes")
 EXPORTS = tuple(_SIGS.keys())
 _libs = {}
 

@@ -575,3 +575,139 @@ def make_render_inputs(case, seed=None):
         raise ValueError(case)
     return dict(vertices=[m[0] for m in meshes], faces=[m[1] for m in meshes], labels=labels, R=R, t=t, K=np.repeat(K[None], N, axis=0),
                 H=H, W=W, near=near, far=far, seed=seed)
+
+
+# ----------------------------------------------------------------------------------------------
+# scenes of the BOP errors (gdrnet_amd.bop_metrics, golden G14)
+# ----------------------------------------------------------------------------------------------
+BOP_METRIC_SEEDS = {"vsd": 151, "sym": 152}
+# ^ the seeds golden G14 was drawn with (tests/golden/make_golden_g14.py moves on while a decision of the reference sits within rounding of its threshold)
+BOP_VSD_DELTA = 0.015   # BOP's 15 mm
+
+
+def make_bop_metric_inputs(case, seed=None):
+    """Inputs of the BOP-error golden G14 (gdrnet_amd.bop_metrics against lib/pysixd/pose_error.py vsd / mssd / mspd), fp64, metres.
+
+    "vsd"  12 rows in 3 test frames of 47 x 61 (a ragged last chunk and wave), four per frame, one per quadrant, over three mesh classes -- 0: a
+           0.1 m cube, 1: the perturbed icosphere (subdivision 3), 2: a 0.12 x 0.09 m rectangle of 8 x 8 cells -- with a skew-free K per row (frame 2
+           has another camera than frames 0 and 1).  Rows: 0 est = gt exactly | 3 est shifted off the object (empty intersection) | 4 est outside the
+           frame | 5 gt hidden behind an occluder by more than delta, est with it (empty union) | the others est = gt rotated by 3 .. 25 degrees and
+           shifted by up to 6 cm, mostly along the ray.  ``bop_test_depth`` makes the test images from the rows' ground-truth depth maps:
+           the nearest surface per frame in front of a background plane, an occluder over the left half of row 1's object and over all of row 5's,
+           a block of zero-depth holes over part of row 6's, +-2 mm hash noise.
+    "sym"  41 rows cycling through four classes -- 0: 1031 points, 314 transformations (continuous about an axis that misses the origin); 1: 257
+           points, 3 (the identity and two discrete ones with a translation part); 2: ONE point, the identity only (syms None); 3: 8195 points, 314
+           -- estimates graded as in make_pose_metric_inputs("A") (times one of the class's transformations on every fourth row), rows 0 and 6 with
+           est = gt (row 0, class 0: the reference's set of a continuous symmetry leaves the identity out, so its error is one rotation step, not 0),
+           rows 5 and 8 with est = gt o S_k exactly for a k > 0, per-row K near the LM camera, 3 targets without an estimate."""
+    from .bop_metrics import symmetry_transformations
+
+    seed = BOP_METRIC_SEEDS[case] if seed is None else seed
+    u = lambda tag, *shape: hash_uniform(seed, tag, shape)  # noqa: E731
+    if case == "vsd":
+        H, W, N = 47, 61, 12
+        rv, rf = mesh_rectangle(8, 8)
+        meshes = [mesh_cube(0.1), mesh_icosphere(3, 0.05, 0.35, seed), (rv * np.array([0.12, 0.09, 1.0]), rf)]
+        diam = np.array([0.1 * math.sqrt(3.0), 0.115, 0.15])
+        labels = np.arange(N, dtype=np.int64) % 3
+        frame = np.arange(N, dtype=np.int64) // 4
+        K1 = np.array([[70.0, 0.0, 30.3], [0.0, 71.0, 23.4], [0.0, 0.0, 1.0]])
+        K2 = np.array([[64.5, 0.0, 29.1], [0.0, 63.0, 22.2], [0.0, 0.0, 1.0]])
+        K = np.stack([K2 if f == 2 else K1 for f in frame])
+        R_gt = _random_rotations(seed, "R_gt", N)
+        for i in range(N):
+            if labels[i] == 2:   # the rectangle: roughly facing the camera
+                ax = hash_normal(seed, f"tilt{i}", (1, 3))
+                R_gt[i] = _axis_angle(ax / np.linalg.norm(ax), np.array([25.0]))[0]
+        z = 0.42 + 0.1 * u("t_z", N)
+        centre = np.array([[15.0, 12.0], [45.0, 12.0], [15.0, 35.0], [45.0, 35.0]])[np.arange(N) % 4] + 3.0 * (u("t_px", N, 2) - 0.5)
+        t_gt = np.stack([(centre[:, 0] - K[:, 0, 2]) / K[:, 0, 0] * z, (centre[:, 1] - K[:, 1, 2]) / K[:, 1, 1] * z, z], axis=1)
+        ang = 3.0 + 22.0 * u("ang", N)
+        axis = hash_normal(seed, "axis", (N, 3))
+        axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+        R_est = _axis_angle(axis, ang) @ R_gt
+        dz = np.array([0.0, 0.012, -0.02, 0.0, 0.0, 0.01, 0.03, -0.045, 0.06, -0.008, 0.022, 0.04])
+        t_est = t_gt * (1.0 + dz / z)[:, None] + 0.004 * (u("t_jit", N, 3) - 0.5)
+        R_est[0], t_est[0] = R_gt[0], t_gt[0]
+        R_est[3], t_est[3] = R_gt[3], t_gt[3] - np.array([0.2, 0.0, 0.0])   # (towards the frame's middle: it stays in view)
+        t_est[4] = t_gt[4] + np.array([2.0, 0.0, 0.0])
+        return dict(vertices=[m[0] for m in meshes], faces=[m[1] for m in meshes], diameters=diam, labels=labels, frame=frame, num_frames=3,
+                    R_est=R_est, t_est=t_est, R_gt=R_gt, t_gt=t_gt, K=K, H=H, W=W, near=0.01, far=6.5, delta=BOP_VSD_DELTA,
+                    taus=np.arange(0.05, 0.51, 0.05), background=1.5, occluded={1: "left", 5: "all"}, holes_row=6, noise=0.002, seed=seed)
+    if case != "sym":
+        raise ValueError(case)
+    N, sizes, diam = 41, (1031, 257, 1, 8195), [0.2, 0.3, 0.1, 0.25]
+    rz, rx = np.diag([-1.0, -1.0, 1.0]), np.diag([1.0, -1.0, -1.0])
+
+    def hom(R, t):
+        m = np.eye(4)
+        m[:3, :3], m[:3, 3] = R, t
+        return m.ravel().tolist()
+
+    model_infos = [
+        {"diameter": diam[0], "symmetries_continuous": [{"axis": [0, 0, 1], "offset": [0.01, -0.02, 0.0]}]},
+        {"diameter": diam[1], "symmetries_discrete": [hom(rz, [0.01, -0.02, 0.0]), hom(rx, [0.0, 0.015, 0.005])]},
+        {"diameter": diam[2]},
+        {"diameter": diam[3], "symmetries_continuous": [{"axis": [0.6, 0.0, 0.8], "offset": [0.0, 0.03, 0.01]}]},
+    ]
+    syms = [symmetry_transformations(m) if len(m) > 1 else None for m in model_infos]
+    points = [-0.1 + 0.2 * u(f"pts{c}", n, 3) for c, n in enumerate(sizes)]
+    labels = np.arange(N, dtype=np.int64) % len(sizes)
+    R_gt = _random_rotations(seed, "R_gt", N)
+    t_gt = np.concatenate([0.3 * u("t_xy", N, 2) - 0.15, 0.6 + 0.8 * u("t_z", N, 1)], axis=1)
+    q = u("quality", N)
+    ang = 0.1 * 200.0 ** (0.7 * q + 0.3 * u("q_ang", N))
+    off = 0.15 * (0.7 * q + 0.3 * u("q_off", N)) ** 2
+    axis = hash_normal(seed, "axis", (N, 3))
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    tdir = hash_normal(seed, "tdir", (N, 3))
+    tdir /= np.linalg.norm(tdir, axis=1, keepdims=True)
+    R_est = _axis_angle(axis, ang) @ R_gt
+    t_est = t_gt + off[:, None] * tdir
+    for i in range(N):
+        s = syms[labels[i]]
+        if s is not None and (i // len(sizes)) % 4 == 3:   # the estimate lands near another member of the symmetry set
+            k = int(u(f"k{i}", 1)[0] * len(s[0]))
+            R_est[i], t_est[i] = R_est[i] @ s[0][k], R_est[i] @ s[1][k] + t_est[i]
+    for i in (0, 6):
+        R_est[i], t_est[i] = R_gt[i], t_gt[i]
+    for i, k in ((5, 2), (8, 200)):   # class 1, its last transformation | class 0, deep in the table
+        S = syms[labels[i]]
+        R_est[i], t_est[i] = R_gt[i] @ S[0][k], R_gt[i] @ S[1][k] + t_gt[i]
+    K = np.repeat(LM_K.astype(np.float64)[None], N, axis=0)
+    K[:, 0, 0] += 4.0 * (u("fx", N) - 0.5)
+    K[:, 1, 1] += 4.0 * (u("fy", N) - 0.5)
+    K[:, :2, 2] += 6.0 * (u("c", N, 2) - 0.5)
+    return dict(points=points, diameters=np.array(diam), model_infos=model_infos, syms=syms, obj_names=["can", "box", "dot", "bowl"], labels=labels,
+                R_est=R_est, t_est=t_est, R_gt=R_gt, t_gt=t_gt, K=K, im_width=640, missing={0: 2, 2: 1}, exact_rows={6: 0, 5: 2, 8: 200}, seed=seed)
+
+
+def bop_test_depth(inp, depth_gt):
+    """The test images [F,H,W] fp32 of a make_bop_metric_inputs("vsd") scene from its rows' ground-truth depth maps ``depth_gt`` [N,H,W] (the host
+    rasterizer's or the device's: they hold the same bits): per frame the nearest ground-truth surface, ``background`` where there is none; an
+    occluder 0.1 m in front of the left half (row 1) / of all (row 5) of an object's bounding box, grown by 8 pixels all round for "all" so that a
+    displaced estimate stays behind it; a 5 x 4 block of zero-depth holes from the centre of row 6's bounding box; then +-``noise`` m of hash noise on
+    every valid pixel and one rounding to fp32."""
+    depth_gt = np.asarray(depth_gt, dtype=np.float64)
+    N, H, W = depth_gt.shape
+    out = np.full((inp["num_frames"], H, W), float(inp["background"]))
+    for i in range(N):
+        f, d = int(inp["frame"][i]), depth_gt[i]
+        out[f] = np.where((d > 0) & (d < out[f]), d, out[f])
+
+    def bbox(i):
+        ys, xs = np.nonzero(depth_gt[i] > 0)
+        return int(xs.min()), int(ys.min()), int(xs.max()), int(ys.max())
+
+    for i, how in inp["occluded"].items():
+        x1, y1, x2, y2 = bbox(i)
+        if how == "left":
+            x2 = (x1 + x2) // 2
+        else:
+            x1, y1, x2, y2 = max(x1 - 8, 0), max(y1 - 8, 0), min(x2 + 8, W - 1), min(y2 + 8, H - 1)
+        out[int(inp["frame"][i]), y1 : y2 + 1, x1 : x2 + 1] = depth_gt[i][depth_gt[i] > 0].min() - 0.1
+    out += inp["noise"] * (2.0 * hash_uniform(inp["seed"], "test_noise", out.shape) - 1.0)
+    x1, y1, x2, y2 = bbox(inp["holes_row"])
+    cx, cy = (x1 + x2) // 2, (y1 + y2) // 2
+    out[int(inp["frame"][inp["holes_row"]]), cy : cy + 4, cx : cx + 5] = 0.0
+    return out.astype(np.float32)

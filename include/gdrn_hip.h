@@ -789,6 +789,63 @@ int gdrn_render_depth(const double* verts, const int* faces, const int* vert_off
 int gdrn_xyz_from_depth(const float* depth, const double* R, const double* t, const double* K, int N, int H, int W, float* xyz,
                         unsigned char* mask, int* xyxy, int* visible, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * BOP pose errors (VSD, MSSD, MSPD) and their recall counts (added within ABI 5: new entry points, nothing changed): what the reference gets by
+ * writing a CSV and running the BOP toolkit on the host (core/gdrn_modeling/gdrn_evaluator.py:437-514 -> lib/pysixd/scripts/eval_calc_errors.py:344-372
+ * with lib/pysixd/pose_error.py:84-179, then eval_calc_scores.py) -- for N estimates per call, one estimate per ground-truth target.  Units: metres
+ * and pixels.  Every decision and every output is fp64 except the fp32 visibility difference noted below; no floating-point atomics (integer counts;
+ * fp64 sums and minima as per-workgroup partials finished in a fixed order): repeated calls give the same bits, and a row's result does not depend
+ * on the other rows of the call.  The speed shortcuts of eval_calc_errors.py:328-347,366-367 (VSD = 1 / MSSD = inf for bounding spheres that do
+ * not overlap) are NOT applied: the errors are the functions' values.
+ *
+ * gdrn_vsd (pose_error.py:84-126, visibility.py:27-36,72-73 in "bop19" mode, misc.py:565-588):
+ *   depth_est, depth_gt [N][H][W] fp32: the model under the estimated / the ground-truth pose, the output layout of gdrn_render_depth (0 = nothing);
+ *   depth_test [F][H][W] fp32: the test images' depth (0 = missing);  frame [N] int32 (device): the test image of row i, several rows may share
+ *   one;  frame_host: the same N values in host memory, checked against [0, F) before anything is launched (GDRN_ERR_ARG);  K [N][3][3] fp64, read
+ *   as fx = K[0][0], cx = K[0][2], fy = K[1][1], cy = K[1][2] -- K[0][1] (skew) is NOT read, as in misc.py:565-566;  diameter [N] fp64 (per ROW);
+ *   taus [T] fp64 (device), T <= GDRN_VSD_MAX_TAUS;  cost_type GDRN_VSD_STEP | GDRN_VSD_TLINEAR.
+ *   Per pixel (x, y): dist = sqrt((X d)^2 + (Y d)^2 + d^2) in fp64 of each of the three depths d, X = (x - cx) / fx, Y = (y - cy) / fy;
+ *     visib_gt  = ((float)dist_gt - (float)dist_test <= (float)delta  or  dist_test == 0)  and  dist_gt > 0     -- the difference in fp32, as the
+ *                 reference takes it; delta rounded to fp32 as numpy compares an fp32 array with a Python float
+ *     visib_est = (the same with dist_est)  or  (visib_gt and dist_est > 0)
+ *     dists     = |dist_gt - dist_est| on visib_gt and visib_est, divided by diameter when normalized_by_diameter != 0
+ *     cost      = dists >= tau (step)  |  min(dists / tau, 1) (tlinear)
+ *   err [N][T] = (sum of costs + |union| - |intersection|) / |union|, 1.0 for every tau when the union is empty.
+ *   counts [N][2 + T] int64 = |union|, |union| - |intersection|, and per tau the STEP cost count (whatever cost_type); cleared inside the call.
+ *   A pixel where both model depths are 0 is in neither mask and is skipped.  The tlinear sum is taken in a fixed order that is not numpy's: it
+ *   agrees with it to about (|intersection| + 4) 2^-52 relative; the step error is one division of two exact integers.
+ *   workspace: gdrn_vsd_workspace_bytes(N, H, W, T) bytes of device memory, no initialisation needed.
+ *
+ * gdrn_mssd_mspd (pose_error.py:131-179): poses, K (all of it: misc.project_pts multiplies by the whole matrix), labels and labels_host as in
+ *   gdrn_pose_errors;  pts [C][n_max][3] fp64 with npts [C] valid rows each;  sym_R [C][S_max][3][3], sym_t [C][S_max][3] fp64 with nsym [C] >= 1
+ *   valid transformations each (the identity included where it belongs: misc.get_symmetry_transformations).  Rows beyond npts[c] and
+ *   transformations beyond nsym[c] never enter a result.  err [N][2] = (MSSD in metres, MSPD in pixels): the minimum over the class's
+ *   transformations (R_gt S, R_gt t_S + t_gt) of the maximum over its points of the distance to the estimate-posed point, in 3D and in the image.
+ *   A NaN in a pose gives NaN (never a hang); nsym[c] = 0 gives NaN.  Work is spread over (row, slab of 8 transformations), the slabs' minima are
+ *   finished in slab order.  workspace: gdrn_mssd_mspd_workspace_bytes(N, n_max, S_max) bytes, no initialisation needed.
+ *
+ * gdrn_bop_recall_accumulate: adds a batch (vsd_err [N][T] from gdrn_vsd, mssd_mspd_err [N][2]) to the caller's per-class state (device memory,
+ *   zeroed by the caller before the first call), GDRN_BOP_NTH = 10 thresholds each, passed as fp64 device arrays (eval_pose_results_more.py:58-63:
+ *   np.arange(0.05, 0.51, 0.05) twice and np.arange(5, 51, 5)), strict <:
+ *     hits_vsd [C][T][10] += vsd < ths_vsd[k];   hits_mssd [C][10] += mssd / diameter[c] < ths_mssd[k]   (diameter [C] fp64, per CLASS);
+ *     hits_mspd [C][10] += (640 / im_width) mspd < ths_mspd[k]   (eval_calc_scores.py:239-250);   seen [C] += rows of the class.
+ *   One workgroup per class, integer adds; calls on one stream follow each other. */
+#define GDRN_VSD_MAX_TAUS 32
+#define GDRN_BOP_NTH 10
+enum { GDRN_VSD_STEP = 0, GDRN_VSD_TLINEAR = 1 };
+long long gdrn_vsd_workspace_bytes(int N, int H, int W, int T);
+int gdrn_vsd(const float* depth_est, const float* depth_gt, const float* depth_test, const int* frame, const int* frame_host, int F,
+             const double* K, const double* diameter, int N, int H, int W, double delta, const double* taus, int T, int cost_type,
+             int normalized_by_diameter, double* err, long long* counts, void* workspace, void* stream);
+long long gdrn_mssd_mspd_workspace_bytes(int N, int n_max, int S_max);
+int gdrn_mssd_mspd(const double* R_est, const double* t_est, const double* R_gt, const double* t_gt, const double* K, const int* labels,
+                   const int* labels_host, int N, const double* pts, const int* npts, int n_max, const double* sym_R, const double* sym_t,
+                   const int* nsym, int S_max, int C, double* err, void* workspace, void* stream);
+int gdrn_bop_recall_accumulate(const double* vsd_err, int T, const double* mssd_mspd_err, const int* labels, const int* labels_host, int N,
+                               const double* diameter, int C, double im_width, const double* ths_vsd, const double* ths_mssd,
+                               const double* ths_mspd, long long* hits_vsd, long long* hits_mssd, long long* hits_mspd, long long* seen,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
