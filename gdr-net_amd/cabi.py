@@ -128,6 +128,17 @@ class RoiTask(C.Structure):
     ]
 
 
+class AugTask(C.Structure):
+    """gdrn_aug_task: one frame of csrc/augment.hip (background replacement + colour augmentation)"""
+    _fields_ = [
+        ("frame", P), ("mask", P), ("bg", P), ("out", P), ("mask_trunc", P),
+        ("inv_scale", D), ("trunc_u", D),
+        ("H", I), ("W", I), ("bg_h", I), ("bg_w", I), ("ch", I), ("cw", I), ("oh", I), ("ow", I),
+        ("trunc_mode", I), ("gh", I), ("gw", I), ("keep_off", I), ("lut_off", I), ("blur_r", I),
+        ("blur_w", F * 9),
+    ]
+
+
 def to_device_table(structs, device):
     """ctypes struct list -> uint8 device tensor holding the C array."""
     import torch
@@ -248,6 +259,8 @@ _SIGS = {
     "gdrn_mssd_mspd_workspace_bytes": [I, I, I],
     "gdrn_mssd_mspd": [P, P, P, P, P, P, P, I, P, P, I, P, P, P, I, I, P, P, P],
     "gdrn_bop_recall_accumulate": [P, I, P, P, P, I, P, I, D, P, P, P, P, P, P, P, P],
+    "gdrn_aug_mask_cuts": [P, C.POINTER(AugTask), I, P, P],
+    "gdrn_aug_frames": [P, C.POINTER(AugTask), I, P, LL, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []

@@ -184,10 +184,36 @@ def lm13_cfg(device="cuda", **over):
     return cfg
 
 
+def _frame_aug_input():
+    """INPUT keys of the background / colour augmentation block (gdrnet_amd.augment), the values both shipped LM-O / YCB-V training configs
+    set (configs/gdrn/lmo/a6_cPnP_AugAAETrunc_BG0.5_lmo_real_pbr0.1_40e.py:6-22; the YCB-V file named below: the same lines) over
+    configs/_base_/common_base.py:46.  COLOR_AUG_OPS is the chain of COLOR_AUG_CODE (:15-21, random_order=False :22) in this project's
+    structured notation: prob = the Sometimes probability, ("rand", k) = k * U[0, 1) drawn once per augmenter (the code string's
+    ``1.2*np.random.rand()`` is evaluated once, when the augmenter is built).  A non-empty INPUT.COLOR_AUG_CODE string, where a caller sets
+    one, takes precedence over COLOR_AUG_OPS (augment.parse_color_aug_code)."""
+    return dict(
+        CHANGE_BG_PROB=0.5,            # :7
+        TRUNCATE_FG=True,              # :6
+        BG_KEEP_ASPECT_RATIO=True,     # common_base.py:46
+        COLOR_AUG_PROB=0.8,            # :8
+        COLOR_AUG_TYPE="code",         # :9
+        COLOR_AUG_OPS=[
+            dict(op="CoarseDropout", prob=0.5, p=0.2, size_percent=0.05),            # :15
+            dict(op="GaussianBlur", prob=0.5, sigma=("rand", 1.2)),                  # :16
+            dict(op="Add", prob=0.5, value=(-25, 25), per_channel=0.3),              # :17
+            dict(op="Invert", prob=0.3, p=0.2, per_channel=1.0),                     # :18
+            dict(op="Multiply", prob=0.5, value=(0.6, 1.4), per_channel=0.5),        # :19
+            dict(op="Multiply", prob=0.5, value=(0.6, 1.4), per_channel=0.0),        # :20
+            dict(op="LinearContrast", prob=0.5, value=(0.5, 2.2), per_channel=0.3),  # :21
+        ],
+    )
+
+
 def lmo_cfg(device="cuda", **over):
     """LM-O config (configs/gdrn/lmo/a6_cPnP_AugAAETrunc_BG0.5_lmo_real_pbr0.1_40e.py): same graph, 8 classes."""
     cfg = lm13_cfg(device)
     cfg.MODEL.CDPN.ROT_HEAD.NUM_CLASSES = 8
+    cfg.INPUT.merge(_frame_aug_input())
     cfg.merge(over)
     return cfg
 
@@ -198,5 +224,6 @@ def ycbv_cfg(device="cuda", **over):
     cfg = lm13_cfg(device)
     cfg.MODEL.CDPN.ROT_HEAD.NUM_CLASSES = 21
     cfg.MODEL.CDPN.PNP_NET.PM_LOSS_SYM = True
+    cfg.INPUT.merge(_frame_aug_input())
     cfg.merge(over)
     return cfg

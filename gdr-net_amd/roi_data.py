@@ -9,9 +9,9 @@ object-coordinate patches and the masks are device tensors, and ONE ``gdrn_roi_a
 ``roi_region`` [B,64,64], ``roi_wh``, ``resize_ratio``, ``trans_ratio`` ...), so at >20 k RoI/s per GPU the batch
 never has to pass through cv2 on 4 CPU workers (common_base.py:87).
 
-What stays on the host, as in the reference: file decoding, colour / background augmentation, the random DZI box
-jitter (``aug_bbox``, base_data_loader.py:120-152 -- its *result* ``bbox_center`` / ``scale`` is an input here) and
-the scalar per-instance bookkeeping.  ``INPUT.SMOOTH_XYZ`` / ``TRAIN.VIS`` (median-blurred / bilinear xyz) and the
+What stays on the host, as in the reference: file decoding, the random DZI box jitter (``aug_bbox``,
+base_data_loader.py:120-152 -- its *result* ``bbox_center`` / ``scale`` is an input here) and the scalar per-instance
+bookkeeping (background replacement and colour augmentation of the frames: ``gdrnet_amd.augment``).  ``INPUT.SMOOTH_XYZ`` / ``TRAIN.VIS`` (median-blurred / bilinear xyz) and the
 classification (``CE``) xyz targets are not on the path and raise ``NotImplementedError``.  There is no CPU fallback.
 """
 import ctypes as C

@@ -335,6 +335,28 @@ def make_roi_frames(B=8, seed=5, ncls=13, nfps=64, frame_sizes=((480, 640), (540
     return dict(frames=frames, rois=rois, extents=extents, fps_points=fps)
 
 
+AUG_FRAME_SIZES = ((47, 61), (33, 9), (64, 96))
+AUG_BANK_SIZES = ((7, 1000), (100, 37), (375, 500), (481, 640))
+
+
+def make_augment_inputs(seed=15):
+    """Synthetic inputs of the frame augmenter (gdrnet_amd.augment), numpy on the host: u8 frames of 47 x 61, 33 x 9 and 64 x 96 with one
+    foreground mask each (a noisy blob well inside the frame, so that every cut mode changes it), bank images of 7 x 1000, 100 x 37, 375 x 500 and
+    481 x 640 -- between them up- and down-scaling, a zero-padded remainder, tiles cut by the frame edge and a frame narrower than one tile --
+    and ``g15_bg``: the ready-made 47 x 61 background golden G15's composites were drawn with (as a bank image it is resized by exactly 1)."""
+    u = lambda tag, *shape: hash_uniform(seed, tag, shape)  # noqa: E731
+    frames = [np.floor(u(f"aug_frame{i}", h, w, 3) * 256).astype(np.uint8) for i, (h, w) in enumerate(AUG_FRAME_SIZES)]
+    bank = [np.floor(u(f"aug_bank{i}", h, w, 3) * 256).astype(np.uint8) for i, (h, w) in enumerate(AUG_BANK_SIZES)]
+    masks = []
+    for i, (h, w) in enumerate(AUG_FRAME_SIZES):
+        m = np.zeros((h, w), np.uint8)
+        y0, y1, x0, x1 = h // 5, h - h // 4, w // 4, w - w // 5
+        m[y0:y1, x0:x1] = (u(f"aug_mask{i}", y1 - y0, x1 - x0) < 0.8) * (1 + i * 100)   # any non-zero value is foreground
+        masks.append(m)
+    h, w = AUG_FRAME_SIZES[0]
+    return dict(frames=frames, masks=masks, bank=bank, g15_bg=np.floor(u("aug_g15_bg", h, w, 3) * 256).astype(np.uint8), seed=seed)
+
+
 def make_region_inputs(B=4, res=64, nfps=64):
     """Inputs of golden G8 (``xyz_to_region``): cropped object-coordinate maps [B][res][res][3] fp32 with background
     holes, and fps points [B][nfps][3]; batch 1 has a duplicated fps point (argmin tie -> first index) and batch 2

@@ -846,6 +846,58 @@ int gdrn_bop_recall_accumulate(const double* vsd_err, int T, const double* mssd_
                                const double* ths_mspd, long long* hits_vsd, long long* hits_mssd, long long* hits_mspd, long long* seen,
                                void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Background replacement and colour augmentation of whole training frames (added within ABI 5: new entry points, nothing changed): what the
+ * reference does per sample on the host between decoding and cropping -- replace_bg / get_bg_image (core/base_data_loader.py:320-403,
+ * resize_short_edge core/utils/data_utils.py:161-187) and the imgaug chain of INPUT.COLOR_AUG_CODE (core/gdrn_modeling/data_loader.py:319-343) --
+ * for a batch of frames of any sizes per call.  Every random decision is made by the caller and arrives in the task; the kernels are deterministic.
+ *
+ * One gdrn_aug_task per frame, the same table twice: as a device array for the kernels and as a host array for the argument checks.  Frames are
+ * u8 [H][W][3].  The stages, in this order, on the full frame:
+ *   background   (mask != NULL) the top-left ch x cw crop of the bank image bg (u8, rows of bg_w pixels) resized by 1 / inv_scale with cv2's 8-bit
+ *                bilinear rule, sampled per pixel: f = (float)((x + 0.5) inv_scale - 0.5), s = floor(f), f -= s; s < 0 -> s = 0, f = 0; s >= cw - 1 ->
+ *                s = cw - 1, f = 0; second tap clamped to cw - 1; a0 = rint((1.f - f) 2048), a1 = rint(f 2048); the same in y (ch; b0, b1);
+ *                S_r = p[r][s] a0 + p[r][s + 1] a1 (int32); value = (((b0 (S_0 >> 4)) >> 16) + ((b1 (S_1 >> 4)) >> 16) + 2) >> 2.  Pixels with
+ *                y >= oh or x >= ow are 0 (oh <= H, ow <= W: the caller's rounding of the resized size).
+ *   cut          gdrn_aug_mask_cuts finds the inclusive bounds r_min, r_max, c_min, c_max of mask != 0 and with c_h = 0.5 (r_min + r_max),
+ *                c_w = 0.5 (c_min + c_max) in fp64 and u = trunc_u clears, by trunc_mode: 0 rows < int(r_min + (c_h - r_min) u);  1 rows >=
+ *                int(c_h + (r_max - c_h) u);  2 columns < int(c_min + (c_w - c_min) u);  3 columns >= int(c_w + (c_max - c_w) u);  4 nothing.
+ *                cuts [B][4] int32 = the kept half-open ranges (row_lo, row_hi, col_lo, col_hi); an empty mask keeps nothing (0, 0, 0, 0).
+ *   composite    mask_trunc = mask != 0 inside the kept ranges (written as 0 / 1 when mask_trunc != NULL);  v = mask_trunc ? frame : background
+ *   dropout      (gh > 0) pixel (y, x) belongs to cell (min(floor(y gh / H), gh - 1), min(floor(x gw / W), gw - 1)) (fp64); a cell whose byte in
+ *                the keep grid aux[keep_off ...] ([gh][gw] u8) is 0 becomes 0 in all channels.  gh gw <= GDRN_AUG_MAX_CELLS.
+ *   blur         (blur_r in 1 .. GDRN_AUG_MAX_RADIUS; H, W > blur_r) separable, weights blur_w[0 .. 2 blur_r] fp32, reflect-101 borders, horizontal
+ *                then vertical in fp32, taps accumulated left to right / top to bottom (acc = w0 p0; acc = acc + w1 p1; ... every product and sum
+ *                rounded on its own), no rounding between the passes, then rint (half to even) and a clamp to 0 .. 255.
+ *   table        (lut_off >= 0) out = aux[lut_off + c 256 + v] per channel c: the frame's point operations composed by the caller.
+ * aux: one device byte array of aux_bytes holding every keep grid and table of the batch; keep_off / lut_off are byte offsets into it, -1 = none.
+ * gdrn_aug_mask_cuts: one workgroup per frame, frames with mask == NULL are left alone.  gdrn_aug_frames: one workgroup per 32 x 32 output tile,
+ *   the grid sized by the largest frame; reads cuts for frames with a mask (so it follows gdrn_aug_mask_cuts on the stream).
+ * Status: GDRN_ERR_ARG for a NULL table / B <= 0 / a task with a missing pointer, a non-positive size, a crop outside its bank image, an offset
+ *   outside aux, a mode outside 0..4 or a frame side <= blur_r;  GDRN_ERR_SHAPE for a radius above GDRN_AUG_MAX_RADIUS, a grid above
+ *   GDRN_AUG_MAX_CELLS or B > 65535.  Checked on the host table before anything is launched; neither call allocates or reads anything back. */
+#define GDRN_AUG_MAX_CELLS 4096
+#define GDRN_AUG_MAX_RADIUS 4
+typedef struct gdrn_aug_task {
+    const unsigned char* frame;      /* [H][W][3] u8 */
+    const unsigned char* mask;       /* [H][W] u8, any non-zero = foreground; NULL: the background stays */
+    const unsigned char* bg;         /* bank image, u8 rows of bg_w pixels x 3 (with mask) */
+    unsigned char* out;              /* [H][W][3] u8 */
+    unsigned char* mask_trunc;       /* [H][W] u8 0 / 1, or NULL */
+    double inv_scale;                /* 1 / s of the background resize */
+    double trunc_u;
+    int H, W;
+    int bg_h, bg_w, ch, cw, oh, ow;  /* bank image size, crop size, resized size clamped to the frame */
+    int trunc_mode;                  /* 0 .. 4 */
+    int gh, gw, keep_off;            /* dropout grid, 0 / 0 / -1 = none */
+    int lut_off;                     /* -1 = none */
+    int blur_r;                      /* 0 = none */
+    float blur_w[9];
+} gdrn_aug_task;
+int gdrn_aug_mask_cuts(const gdrn_aug_task* tasks_dev, const gdrn_aug_task* tasks_host, int B, int* cuts, void* stream);
+int gdrn_aug_frames(const gdrn_aug_task* tasks_dev, const gdrn_aug_task* tasks_host, int B, const unsigned char* aux, long long aux_bytes,
+                    const int* cuts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
