@@ -139,6 +139,14 @@ class AugTask(C.Structure):
     ]
 
 
+class RleTask(C.Structure):
+    """gdrn_rle_task: one mask of csrc/rle.hip (COCO run-length strings <-> masks)"""
+    _fields_ = [
+        ("mask", P), ("sy", LL), ("sx", LL), ("str_off", LL), ("run_off", LL), ("seg_off", LL),
+        ("str_len", I), ("h", I), ("w", I), ("pad_", I),
+    ]
+
+
 def to_device_table(structs, device):
     """ctypes struct list -> uint8 device tensor holding the C array."""
     import torch
@@ -261,6 +269,10 @@ _SIGS = {
     "gdrn_bop_recall_accumulate": [P, I, P, P, P, I, P, I, D, P, P, P, P, P, P, P, P],
     "gdrn_aug_mask_cuts": [P, C.POINTER(AugTask), I, P, P],
     "gdrn_aug_frames": [P, C.POINTER(AugTask), I, P, LL, P, P],
+    "gdrn_rle_decode": [P, C.POINTER(RleTask), I, P, LL, P, LL, P, P, P],
+    "gdrn_rle_count": [P, C.POINTER(RleTask), I, P, LL, P, P, P],
+    "gdrn_rle_positions": [P, C.POINTER(RleTask), I, P, LL, P, P, LL, P],
+    "gdrn_rle_string": [P, C.POINTER(RleTask), I, P, P, LL, P, P, LL, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []

@@ -898,6 +898,56 @@ int gdrn_aug_mask_cuts(const gdrn_aug_task* tasks_dev, const gdrn_aug_task* task
 int gdrn_aug_frames(const gdrn_aug_task* tasks_dev, const gdrn_aug_task* tasks_host, int B, const unsigned char* aux, long long aux_bytes,
                     const int* cuts, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * COCO run-length masks, decoded and encoded on the device (added within ABI 5: new entry points, nothing changed): what the reference does per
+ * sample on the host with pycocotools -- cocosegm2mask / rle2mask (lib/utils/mask_utils.py:93-125; core/gdrn_modeling/data_loader.py:79,326,332),
+ * binary_mask_to_rle (mask_utils.py:54-66; gdrn_evaluator.py:695-697) and mask2bbox_xyxy (mask_utils.py:39-44) -- for a batch of masks of any
+ * sizes per call.  Everything is integer and exact.
+ *
+ * The format is maskApi's.  An h x w mask is scanned column-major (p = x h + y); counts are the lengths of the alternating runs, the first a run of
+ * zeros (of length 0 when pixel (0, 0) is set; zero-length runs may occur anywhere in an input).  The string stores counts[i] for i <= 2 and
+ * counts[i] - counts[i - 2] behind, each value least-significant first in 5-bit groups as the character 48 + group, bit 0x20 = another group
+ * follows; the last group is the first at which the remaining value (arithmetic shifts) is 0 with bit 0x10 clear or -1 with bit 0x10 set, and on
+ * reading a last group with bit 0x10 set sign-extends the value.  counts are uint32 (sums wrap as maskApi's do); h w < 2^31.
+ *
+ * One gdrn_rle_task per mask, the same table twice: as a device array for the kernels and as a host array for the argument checks.
+ * gdrn_rle_decode: strings (strings_bytes of them; a mask's string is str_len characters at str_off) -> mask [h][w] u8 0 / 1, contiguous (sx = 1,
+ *   sy = w).  run_ends: workspace of run_cap int32, a mask's run ends (clamped to h w) at run_off, room for str_len of them;  nruns [N] int32 and
+ *   totals [N] int64 (the unclamped sum of a mask's counts: the caller may compare it with h w) are outputs.  Whatever the string says, nothing is
+ *   written outside the h w bytes of a mask: pixels behind the last run are 0, runs behind h w are dropped.  Two launches: one workgroup per mask
+ *   (parse), one per 64 x 64 tile (fill).
+ * gdrn_rle_count: mask (any non-zero = foreground; byte strides sy between rows, sx between pixels) -> the transition count of every (column,
+ *   16-row segment) in seg_counts (seg_cap int32; a mask's w ceil(h / 16) counts at seg_off, column-major; NULL: not wanted) and area [N] int32,
+ *   bbox [N][4] int32 = x_min, y_min, x_max, y_max inclusive, an empty mask 0, 0, w - 1, h - 1 as gdrn_xyz_from_depth writes it (both NULL: not
+ *   wanted).  A transition is a pixel that differs from its predecessor in scan order, pixel (0, 0) from 0.
+ * gdrn_rle_positions: follows gdrn_rle_count on the stream: scans seg_counts in place (exclusive, scan order), writes ntrans [N] int32 and the
+ *   scan-order index of every transition, ascending, to positions (pos_cap int32; a mask's at run_off, room for h w + 1).
+ * gdrn_rle_string: positions -> the canonical string of rleEncode + rleToString (counts[0] = positions[0], which is 0 when pixel (0, 0) is set;
+ *   counts[i] = positions[i] - positions[i - 1]; the last run ends at h w).  With str_offsets == NULL it writes lengths [N] int64 only; with
+ *   str_offsets [N + 1] int64 (device) it writes mask n's characters at strings + str_offsets[n], never past str_offsets[n + 1] or strings_bytes.
+ * Status: GDRN_ERR_ARG for a NULL table / N <= 0 / a missing pointer, a task with mask == NULL, a non-positive size, a range outside its buffer
+ *   or (decode) a strided mask;  GDRN_ERR_SHAPE for h w >= 2^31 or N > 65535.  Checked on the host table before anything is launched; no call
+ *   allocates or reads anything back. */
+typedef struct gdrn_rle_task {
+    unsigned char* mask;             /* decode: out [h][w] u8;  encode: in, read only */
+    long long sy, sx;                /* byte strides of mask (decode: w, 1) */
+    long long str_off;               /* decode: first character in strings */
+    long long run_off;               /* decode: first run end in run_ends;  encode: first entry in positions */
+    long long seg_off;               /* encode: first entry in seg_counts */
+    int str_len;                     /* decode */
+    int h, w;
+    int pad_;
+} gdrn_rle_task;
+int gdrn_rle_decode(const gdrn_rle_task* tasks_dev, const gdrn_rle_task* tasks_host, int N, const unsigned char* strings, long long strings_bytes,
+                    int* run_ends, long long run_cap, int* nruns, long long* totals, void* stream);
+int gdrn_rle_count(const gdrn_rle_task* tasks_dev, const gdrn_rle_task* tasks_host, int N, int* seg_counts, long long seg_cap, int* area, int* bbox,
+                   void* stream);
+int gdrn_rle_positions(const gdrn_rle_task* tasks_dev, const gdrn_rle_task* tasks_host, int N, int* seg_counts, long long seg_cap, int* ntrans,
+                       int* positions, long long pos_cap, void* stream);
+int gdrn_rle_string(const gdrn_rle_task* tasks_dev, const gdrn_rle_task* tasks_host, int N, const int* ntrans, const int* positions,
+                    long long pos_cap, const long long* str_offsets, unsigned char* strings, long long strings_bytes, long long* lengths,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
