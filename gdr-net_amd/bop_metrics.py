@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from . import cabi, render
+from . import cabi, devargs, render
 
 COST_TYPES = {"step": 0, "tlinear": 1}   # GDRN_VSD_STEP, GDRN_VSD_TLINEAR
 VSD_TAUS = np.arange(0.05, 0.51, 0.05)   # eval_pose_results_more.py:58
@@ -26,6 +26,7 @@ MSSD_THS = np.arange(0.05, 0.51, 0.05)   # :62
 MSPD_THS = np.arange(5, 51, 5).astype(np.float64)   # :63
 NTH = 10
 MAX_TAUS = 32                            # GDRN_VSD_MAX_TAUS
+WHERE = "the BOP errors"                 # (this module in devargs' error sentence)
 
 
 def _rotation_about(angle, axis):
@@ -69,25 +70,21 @@ def symmetry_transformations(model_info, max_sym_disc_step=0.01):
     return np.stack([R for R, _ in out]), np.stack([t.reshape(3) for _, t in out])
 
 
-class BopModelTable:
+class BopModelTable(devargs.DeviceTables):
     """Per-class tables of MSSD / MSPD and the recall, packed once: ``points`` a list of [n_c,3] arrays (metres), ``diameters`` [C], ``syms`` None or
     per class None (the identity only) / ``(R [S,3,3], t [S,3])`` as ``symmetry_transformations`` returns them.  ``pad_value`` / ``sym_pad_value``
     fill the table rows beyond a class's own points / transformations; the kernels never read them into a result."""
+
+    TABLES = ("pts", "npts", "diameter", "sym_R", "sym_t", "nsym")
 
     def __init__(self, points, diameters, syms=None, pad_value=0.0, sym_pad_value=0.0):
         C = len(points)
         if C == 0 or len(diameters) != C or (syms is not None and len(syms) != C):
             raise ValueError("points, diameters and syms need one entry per class")
-        pts = [np.asarray(p, dtype=np.float64).reshape(-1, 3) for p in points]
-        if any(len(p) == 0 for p in pts):
-            raise ValueError("a class without points has no MSSD / MSPD")
         self.num_classes = C
-        self.npts = np.array([len(p) for p in pts], dtype=np.int32)
-        self.n_max = int(self.npts.max())
-        self.pts = np.full((C, self.n_max, 3), float(pad_value), dtype=np.float64)
-        for c, p in enumerate(pts):
-            self.pts[c, : len(p)] = p
-        self.diameter = np.asarray(diameters, dtype=np.float64).reshape(C).copy()
+        self.pts, self.npts, self.n_max, self.diameter = devargs.pack_points(points, diameters, pad_value)
+        if not self.npts.all():
+            raise ValueError("a class without points has no MSSD / MSPD")
         packed = []
         for c in range(C):
             s = None if syms is None else syms[c]
@@ -104,22 +101,6 @@ class BopModelTable:
         self.sym_t = np.full((C, self.s_max, 3), float(sym_pad_value), dtype=np.float64)
         for c, (R, t) in enumerate(packed):
             self.sym_R[c, : len(R)], self.sym_t[c, : len(t)] = R, t
-        self._dev = {}
-
-    def check_labels(self, labels):
-        """labels (list / numpy / tensor) as a contiguous int32 host array, each within [0, num_classes): raises ValueError otherwise."""
-        host = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
-        host = np.ascontiguousarray(host.reshape(-1).astype(np.int32))
-        if host.size and (host.min() < 0 or host.max() >= self.num_classes):
-            raise ValueError(f"label outside [0, {self.num_classes})")
-        return host
-
-    def on(self, device):
-        """the tables as device tensors (uploaded once per device)."""
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = {k: torch.from_numpy(getattr(self, k)).to(device) for k in ("pts", "npts", "diameter", "sym_R", "sym_t", "nsym")}
-        return self._dev[key]
 
 
 def _f64_vec(v, n, device, what):
@@ -133,26 +114,18 @@ def _f64_vec(v, n, device, what):
     return v
 
 
-def _index(values, n, bound, device, what):
-    """(int32 device tensor, int32 host array) of [n] indices, each within [0, bound): checked on the host before anything is launched; a device
-    tensor is copied back once for it."""
-    host = values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
-    host = np.ascontiguousarray(host.reshape(-1).astype(np.int32))
-    if host.shape[0] != n:
-        raise ValueError(f"{what}: {host.shape[0]} entries for {n} rows")
-    if host.size and (host.min() < 0 or host.max() >= bound):
-        raise ValueError(f"{what} outside [0, {bound})")
-    if isinstance(values, torch.Tensor) and values.device.type == "cuda":
-        return values.detach().reshape(-1).to(torch.int32).contiguous(), host
-    return torch.from_numpy(host).to(device), host
-
-
 def _depth(d, what):
-    if not isinstance(d, torch.Tensor) or d.device.type != "cuda":
-        raise cabi.GdrnHipError(f"the BOP errors run on the GPU (no CPU fallback): {what} is not a device tensor")
+    d = devargs.device_tensor(d, torch.float32, None, what, WHERE)
     if d.dim() != 3:
         raise ValueError(f"{what} must be [n, H, W]")
-    return d.detach().to(torch.float32).contiguous()
+    return d
+
+
+def _gt_poses(R_gt, t_gt, N):
+    R_gt, t_gt = devargs.device_tensor(R_gt, torch.float64, (-1, 3, 3), "R_gt", WHERE), devargs.device_tensor(t_gt, torch.float64, (-1, 3), "t_gt", WHERE)
+    if R_gt.shape[0] != N or t_gt.shape[0] != N:
+        raise ValueError("R_est, t_est, R_gt and t_gt need one entry per row")
+    return R_gt, t_gt
 
 
 def vsd_from_depth(depth_est, depth_gt, depth_test, frame, K, diameters, delta, taus=VSD_TAUS, cost_type="step", normalized_by_diameter=True,
@@ -170,12 +143,8 @@ def vsd_from_depth(depth_est, depth_gt, depth_test, frame, K, diameters, delta, 
         raise ValueError("depth_est and depth_gt are [N,H,W], depth_test is [F,H,W]")
     dev = depth_est.device
     F = int(depth_test.shape[0])
-    K = render._dev(K, torch.float64, (-1, 3, 3), "K")
-    if K.shape[0] == 1 and N > 1:
-        K = K.expand(N, 3, 3).contiguous()
-    if K.shape[0] != N:
-        raise ValueError("K needs one entry per row (or one for all)")
-    fr, fr_host = _index(frame, N, F, dev, "frame")
+    K = devargs.per_row_K(devargs.device_tensor(K, torch.float64, (-1, 3, 3), "K", WHERE), N)
+    fr, fr_host = devargs.index_vector(frame, N, F, dev, "frame")
     diam = _f64_vec(diameters, N, dev, "diameters")
     tau = _f64_vec(taus, None, dev, "taus")
     T = int(tau.shape[0])
@@ -184,14 +153,10 @@ def vsd_from_depth(depth_est, depth_gt, depth_test, frame, K, diameters, delta, 
     lib = cabi.load()
     err = torch.empty(max(N, 1), T, dtype=torch.float64, device=dev)[:N]
     counts = torch.empty(max(N, 1), 2 + T, dtype=torch.int64, device=dev)[:N]
-    ws_bytes = int(lib.gdrn_vsd_workspace_bytes(N, H, W, T))
-    if ws_bytes < 0:
-        cabi.check(ws_bytes, "vsd_workspace_bytes")
-    ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    ws = devargs.workspace(lib.gdrn_vsd_workspace_bytes(N, H, W, T), dev, "vsd_workspace_bytes")
     p = cabi.ptr
     cabi.check(lib.gdrn_vsd(p(depth_est), p(depth_gt), p(depth_test), p(fr), fr_host.ctypes.data, F, p(K), p(diam), N, H, W, float(delta), p(tau), T,
-                            COST_TYPES[cost_type], 1 if normalized_by_diameter else 0, p(err), p(counts), p(ws), st), "vsd")
+                            COST_TYPES[cost_type], 1 if normalized_by_diameter else 0, p(err), p(counts), p(ws), devargs.stream(dev)), "vsd")
     return (err, counts) if return_counts else err
 
 
@@ -200,13 +165,11 @@ def vsd(meshes, labels, R_est, t_est, R_gt, t_gt, K, depth_test, frame, diameter
     """``pose_error.vsd`` of N estimates from their poses: the model ``labels[i]`` of the ``render.MeshTable`` ``meshes`` is rendered under the
     estimated and the ground-truth pose -- all 2N instances with ONE ``render_depth`` call -- and scored by ``vsd_from_depth`` against
     ``depth_test[frame[i]]``.  ``diameters`` [C] PER CLASS of the mesh table.  Poses and K: device tensors, fp32 or fp64.  Nothing is read back."""
-    R_est, t_est, K, N = render._poses(R_est, t_est, K)
-    R_gt, t_gt = render._dev(R_gt, torch.float64, (-1, 3, 3), "R_gt"), render._dev(t_gt, torch.float64, (-1, 3), "t_gt")
-    if R_gt.shape[0] != N or t_gt.shape[0] != N:
-        raise ValueError("R_est, t_est, R_gt and t_gt need one entry per row")
+    R_est, t_est, K, N = devargs.poses(R_est, t_est, K, WHERE)
+    R_gt, t_gt = _gt_poses(R_gt, t_gt, N)
     depth_test = _depth(depth_test, "depth_test")
     dev = R_est.device
-    lab, lab_host = render._labels(meshes, labels, N, dev)
+    lab, lab_host = devargs.index_vector(labels, N, meshes.num_classes, dev, "labels")
     diam = _f64_vec(diameters, meshes.num_classes, dev, "diameters")[lab.long()]
     H, W = int(depth_test.shape[1]), int(depth_test.shape[2])
     both = render.render_depth(meshes, np.concatenate([lab_host, lab_host]), torch.cat([R_est, R_gt]), torch.cat([t_est, t_gt]), torch.cat([K, K]),
@@ -218,22 +181,18 @@ def mssd_mspd(table, R_est, t_est, R_gt, t_gt, K, labels):
     """``pose_error.mssd`` and ``mspd`` (lib/pysixd/pose_error.py:131-179) of N estimates: [N,2] fp64 device tensor, column 0 MSSD in the unit of the
     points, column 1 MSPD in pixels, each the minimum over the symmetry transformations of the class.  R_* [N,3,3], t_* [N,3], K [N,3,3] or [3,3]:
     device tensors, fp32 or fp64; labels [N]: class per row.  A NaN pose gives NaN."""
-    R_est, t_est, K, N = render._poses(R_est, t_est, K)
-    R_gt, t_gt = render._dev(R_gt, torch.float64, (-1, 3, 3), "R_gt"), render._dev(t_gt, torch.float64, (-1, 3), "t_gt")
-    if R_gt.shape[0] != N or t_gt.shape[0] != N:
-        raise ValueError("R_est, t_est, R_gt and t_gt need one entry per row")
+    R_est, t_est, K, N = devargs.poses(R_est, t_est, K, WHERE)
+    R_gt, t_gt = _gt_poses(R_gt, t_gt, N)
     dev = R_est.device
-    lab, lab_host = render._labels(table, labels, N, dev)
+    lab, lab_host = devargs.index_vector(labels, N, table.num_classes, dev, "labels")
     lib = cabi.load()
     tb = table.on(dev)
     err = torch.empty(max(N, 1), 2, dtype=torch.float64, device=dev)[:N]
-    ws_bytes = int(lib.gdrn_mssd_mspd_workspace_bytes(N, table.n_max, table.s_max))
-    ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    ws = devargs.workspace(lib.gdrn_mssd_mspd_workspace_bytes(N, table.n_max, table.s_max), dev, "mssd_mspd_workspace_bytes")
     p = cabi.ptr
     cabi.check(lib.gdrn_mssd_mspd(p(R_est), p(t_est), p(R_gt), p(t_gt), p(K), p(lab), lab_host.ctypes.data, N, p(tb["pts"]), p(tb["npts"]),
-                                  table.n_max, p(tb["sym_R"]), p(tb["sym_t"]), p(tb["nsym"]), table.s_max, table.num_classes, p(err), p(ws), st),
-               "mssd_mspd")
+                                  table.n_max, p(tb["sym_R"]), p(tb["sym_t"]), p(tb["nsym"]), table.s_max, table.num_classes, p(err), p(ws),
+                                  devargs.stream(dev)), "mssd_mspd")
     return err
 
 
@@ -294,22 +253,19 @@ class BopRecall:
         return self._views(self._state)
 
     def update(self, vsd, mssd_mspd, labels):
-        for t, what in ((vsd, "vsd"), (mssd_mspd, "mssd_mspd")):
-            if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-                raise cabi.GdrnHipError(f"the BOP recall runs on the GPU (no CPU fallback): {what} is not a device tensor")
+        vsd = devargs.device_tensor(vsd, torch.float64, None, "vsd", "the BOP recall")
+        mssd_mspd = devargs.device_tensor(mssd_mspd, torch.float64, None, "mssd_mspd", "the BOP recall")
         N = int(vsd.shape[0])
         if vsd.dim() != 2 or vsd.shape[1] != self.T or tuple(mssd_mspd.shape) != (N, 2):
             raise ValueError(f"vsd is [N,{self.T}], mssd_mspd [N,2]")
         dev = vsd.device
-        vsd, mssd_mspd = vsd.detach().to(torch.float64).contiguous(), mssd_mspd.detach().to(torch.float64).contiguous()
-        lab, lab_host = render._labels(self.table, labels, N, dev)
+        lab, lab_host = devargs.index_vector(labels, N, self.table.num_classes, dev, "labels")
         v, tb = self._on(dev), self.table.on(dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
         p = cabi.ptr
         cabi.check(cabi.load().gdrn_bop_recall_accumulate(p(vsd), self.T, p(mssd_mspd), p(lab), lab_host.ctypes.data, N, p(tb["diameter"]),
                                                           self.table.num_classes, self.im_width, p(self._ths[0]), p(self._ths[1]), p(self._ths[2]),
-                                                          p(v["hits_vsd"]), p(v["hits_mssd"]), p(v["hits_mspd"]), p(v["seen"]), st),
-                   "bop_recall_accumulate")
+                                                          p(v["hits_vsd"]), p(v["hits_mssd"]), p(v["hits_mspd"]), p(v["seen"]),
+                                                          devargs.stream(dev)), "bop_recall_accumulate")
 
     def add_missing(self, label, count=1, device=None):
         if not 0 <= int(label) < self.table.num_classes or int(count) < 0:

@@ -11,7 +11,7 @@
 //
 // Everything else is conv3x3_halo.hip's 64-channel tile: 4 waves, wave w owns output channels [16w, 16w + 16) of both convs for all pixels,
 // v_mfma_f32_16x16x32 with the fragment-major weight blocks (gdrn_pack_wfrag, 1 KiB per 16 channels x tap x k-step) streamed L2 -> VGPR through
-// a register ring, pixel operands by ds_read_b128 from the even / odd granule patch layout (PITCH 80: conflict-free for every tap shift).
+// a register ring, pixel operands by ds_read_b128 from the even / odd granule patch layout (HALF_PITCH 80: conflict-free for every tap shift).
 // conv1's pixel fragments are 16 consecutive pixels of the 10 x 18 region in row-major order (12 fragments, the last one 4 pixels), so every
 // fragment has its own lane base (12 registers) and the taps are immediates on top of it, as in the halo kernel.
 // The accumulation order (tap 0..8, k-step 0 then 1) and the epilogue arithmetic (acc + bias (+ identity), ReLU, one rounding to the storage
@@ -26,15 +26,6 @@
 
 namespace {
 
-// compile-time loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>)
-template <class F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
-constexpr int PITCH = 80;   // LDS pixel pitch inside one half array (conv3x3_halo.hip)
-__host__ __device__ constexpr int half_bytes(int ppix) { return (ppix * PITCH + 255) / 256 * 256; }
-
 constexpr int TH = 8, TW = 16;
 constexpr int XW = TW + 4, XH = TH + 4, XPIX = XW * XH;      // input patch 12 x 20
 constexpr int AW = TW + 2, AH = TH + 2, APIX = AW * AH;      // intermediate 10 x 18
@@ -42,10 +33,6 @@ constexpr int HBX = half_bytes(XPIX), HBA = half_bytes(APIX);
 constexpr int XBYTES = 2 * HBX, ABYTES = 2 * HBA;            // 38400 + 29184 = 67584 B: two workgroups per CU
 constexpr int F1 = (APIX + 15) / 16;                         // 12 pixel fragments of conv1
 constexpr int F2 = TH * TW / 16;                             // 8 pixel fragments of conv2
-
-__device__ __forceinline__ f32x4_t mma(uint4 a, uint4 b, f32x4_t c) {
-    return GDRN_MFMA16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c);
-}
 
 __global__ __launch_bounds__(256, 2) void block64_eval_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w1, const float* __restrict__ b1,
                                                               const bf16_t* __restrict__ w2, const float* __restrict__ b2, bf16_t* __restrict__ y,
@@ -92,7 +79,7 @@ __global__ __launch_bounds__(256, 2) void block64_eval_kernel(const bf16_t* __re
         for (int i = 0; i < 8; ++i) {
             const int id = i * 256 + tid;
             const int pp = id >> 3, sg = id & 7;
-            if (id < XPIX * 8) *reinterpret_cast<uint4*>(xp + pp * PITCH + (sg & 1) * HBX + (sg >> 1) * 16) = v[i];
+            if (id < XPIX * 8) *reinterpret_cast<uint4*>(xp + pp * HALF_PITCH + (sg & 1) * HBX + (sg >> 1) * 16) = v[i];
         }
     }
     // lane bases of conv1's pixel fragments: fragment f, lane column r16 -> linear pixel 16 f + r16 of the 10 x 18 region (clamped: the last
@@ -102,7 +89,7 @@ __global__ __launch_bounds__(256, 2) void block64_eval_kernel(const bf16_t* __re
     for (int f = 0; f < F1; ++f) {
         const int L = min(f * 16 + r16, APIX - 1);
         const int py = L / AW, px = L - py * AW;
-        lb1[f] = (py * XW + px) * PITCH + (g & 1) * HBX + (g >> 1) * 16;
+        lb1[f] = (py * XW + px) * HALF_PITCH + (g & 1) * HBX + (g >> 1) * 16;
     }
     __syncthreads();
 
@@ -116,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void block64_eval_kernel(const bf16_t* __re
     uint4 fA[6], fB[6];
     auto rd1 = [&](uint4 (&dst)[6], auto S_) {
         constexpr int s_ = decltype(S_)::value, tap = s_ / 4, ks = (s_ / 2) % 2, half = s_ % 2;
-        constexpr int tsh = ((tap / 3) * XW + (tap % 3)) * PITCH + ks * 32;
+        constexpr int tsh = ((tap / 3) * XW + (tap % 3)) * HALF_PITCH + ks * 32;
 #pragma unroll
         for (int i = 0; i < 6; ++i) dst[i] = *reinterpret_cast<const uint4*>(xp + lb1[half * 6 + i] + tsh);
     };
@@ -130,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void block64_eval_kernel(const bf16_t* __re
         uint4 (&src)[6] = (s_ % 2 == 0) ? fA : fB;
         uint4 (&wq)[2] = (tap % 3 == 0) ? wq0 : ((tap % 3 == 1) ? wq1 : wq2);
 #pragma unroll
-        for (int i = 0; i < 6; ++i) acc1[half * 6 + i] = mma(wq[ks], src[i], acc1[half * 6 + i]);
+        for (int i = 0; i < 6; ++i) acc1[half * 6 + i] = mma_step<bf16_t>(wq[ks], src[i], acc1[half * 6 + i]);
         if constexpr (s_ % 4 == 3) {   // the tap is done: its ring slot takes the weights three taps ahead (running on into conv2's)
             if constexpr (tap + 3 < 9) LOADW(wq, wl1, tap + 3)
             else LOADW(wq, wl2, tap + 3 - 9)
@@ -153,14 +140,14 @@ __global__ __launch_bounds__(256, 2) void block64_eval_kernel(const bf16_t* __re
             const float v0 = fmaxf(acc1[f][0] + bv.x, 0.f), v1 = fmaxf(acc1[f][1] + bv.y, 0.f);
             const float v2 = fmaxf(acc1[f][2] + bv.z, 0.f), v3 = fmaxf(acc1[f][3] + bv.w, 0.f);
             const uint2 o = in ? make_uint2(pack_bf2(v0, v1), pack_bf2(v2, v3)) : make_uint2(0u, 0u);
-            if (L < APIX) *reinterpret_cast<uint2*>(ap + L * PITCH + goff) = o;
+            if (L < APIX) *reinterpret_cast<uint2*>(ap + L * HALF_PITCH + goff) = o;
         }
     }
     __syncthreads();
 
     // ================= conv2 on the tile
-    const int lbase2 = r16 * PITCH + (g & 1) * HBA + (g >> 1) * 16;
-    constexpr int FROW = AW * PITCH;
+    const int lbase2 = r16 * HALF_PITCH + (g & 1) * HBA + (g >> 1) * 16;
+    constexpr int FROW = AW * HALF_PITCH;
     f32x4_t acc2[F2];
 #pragma unroll
     for (int b = 0; b < F2; ++b) acc2[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -168,7 +155,7 @@ __global__ __launch_bounds__(256, 2) void block64_eval_kernel(const bf16_t* __re
     uint4 gA[F2], gB[F2];
     auto rd2 = [&](uint4 (&dst)[F2], auto S_) {
         constexpr int s_ = decltype(S_)::value, tap = s_ / 2, ks = s_ % 2;
-        constexpr int tsh = ((tap / 3) * AW + (tap % 3)) * PITCH + ks * 32;
+        constexpr int tsh = ((tap / 3) * AW + (tap % 3)) * HALF_PITCH + ks * 32;
 #pragma unroll
         for (int b = 0; b < F2; ++b) dst[b] = *reinterpret_cast<const uint4*>(ap + lbase2 + b * FROW + tsh);
     };
@@ -182,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void block64_eval_kernel(const bf16_t* __re
         uint4 (&src)[F2] = (s_ % 2 == 0) ? gA : gB;
         uint4 (&wq)[2] = (tap % 3 == 0) ? wq0 : ((tap % 3 == 1) ? wq1 : wq2);
 #pragma unroll
-        for (int b = 0; b < F2; ++b) acc2[b] = mma(wq[ks], src[b], acc2[b]);
+        for (int b = 0; b < F2; ++b) acc2[b] = mma_step<bf16_t>(wq[ks], src[b], acc2[b]);
         if constexpr (ks == 1 && tap + 3 < 9) LOADW(wq, wl2, tap + 3)
         __builtin_amdgcn_sched_barrier(0);
     });
@@ -196,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void block64_eval_kernel(const bf16_t* __re
         char* yb = reinterpret_cast<char*>(y) + ((size_t)((n * H + y0) * W + x0 + r16) * 64 + wave * 16 + g * 4) * 2;
 #pragma unroll
         for (int b = 0; b < F2; ++b) {
-            const uint2 idn = *reinterpret_cast<const uint2*>(xp + ((b + 2) * XW + r16 + 2) * PITCH + goff);
+            const uint2 idn = *reinterpret_cast<const uint2*>(xp + ((b + 2) * XW + r16 + 2) * HALF_PITCH + goff);
             float v0 = acc2[b][0] + bv.x + h16lo(idn.x), v1 = acc2[b][1] + bv.y + h16hi(idn.x);
             float v2 = acc2[b][2] + bv.z + h16lo(idn.y), v3 = acc2[b][3] + bv.w + h16hi(idn.y);
             v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f);

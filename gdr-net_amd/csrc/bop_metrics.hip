@@ -13,6 +13,7 @@
 // Floating-point contraction is OFF for this file: a*a + b*b + c*c is three products and two sums, as numpy evaluates it, and every fused
 // operation is an explicit fma().  (No 16-bit code: both library builds compile the same thing.)
 #include "common.h"
+#include "geom64.h"
 #include "../../include/gdrn_hip.h"
 
 #pragma clang fp contract(off)
@@ -26,16 +27,6 @@ constexpr int VSD_CHUNK = BM_THREADS * VSD_PPT;      // pixels per workgroup
 constexpr int VSD_MAX_T = GDRN_VSD_MAX_TAUS;
 constexpr int MS_SLAB = 8;                           // symmetry transformations per workgroup
 constexpr int NTH = GDRN_BOP_NTH;
-
-struct V3 { double x, y, z; };
-
-__device__ __forceinline__ V3 xform(const double* R, const double* t, V3 p) {   // R p + t
-    V3 o;
-    o.x = fma(R[0], p.x, fma(R[1], p.y, fma(R[2], p.z, t[0])));
-    o.y = fma(R[3], p.x, fma(R[4], p.y, fma(R[5], p.z, t[1])));
-    o.z = fma(R[6], p.x, fma(R[7], p.y, fma(R[8], p.z, t[2])));
-    return o;
-}
 
 // misc.project_pts (misc.py:511-525): P = K [R | t] (3 x 4), then P [p, 1] divided by its third row
 __device__ __forceinline__ void make_proj(const double* K, const double* R, const double* t, double* P) {
@@ -61,11 +52,6 @@ __device__ __forceinline__ double nanmin(double m, double d) { return (d < m || 
 __device__ __forceinline__ double wave_nanmax(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = nanmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {   // xor tree: a fixed order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
@@ -152,7 +138,7 @@ __global__ __launch_bounds__(BM_THREADS) void vsd_pixels_kernel(const float* __r
                     c = dists / tau;
                     c = c > 1.0 ? 1.0 : c;
                 }
-                c = wave_sum(c);
+                c = wave_sum_f64(c);
                 if (lane == 0) wsum[wave][t] += c;   // this wave's slot only
             }
         }
@@ -208,8 +194,7 @@ __global__ __launch_bounds__(BM_THREADS) void ms_est_kernel(const double* __rest
 #pragma unroll
     for (int k = 0; k < 3; ++k) t[k] = t_est[(size_t)row * 3 + k];
     make_proj(K, R, t, P);
-    const double* pp = pts + ((size_t)c * n_max + j) * 3;
-    const V3 p = {pp[0], pp[1], pp[2]};
+    const V3 p = load3(pts + ((size_t)c * n_max + j) * 3);
     const V3 e = xform(R, t, p);
     double u, v;
     project(P, p, u, v);
@@ -381,12 +366,6 @@ __global__ __launch_bounds__(BM_THREADS) void bop_recall_kernel(const double* __
     }
 }
 
-int in_range(const int* host, int N, int C) {
-    for (int i = 0; i < N; ++i)
-        if (host[i] < 0 || host[i] >= C) return 0;
-    return 1;
-}
-
 long long vsd_chunks(int H, int W) { return ((long long)H * W + VSD_CHUNK - 1) / VSD_CHUNK; }
 
 bool vsd_shape_ok(int N, int H, int W, int T) {
@@ -411,7 +390,7 @@ extern "C" int gdrn_vsd(const float* depth_est, const float* depth_gt, const flo
                         int normalized_by_diameter, double* err, long long* counts, void* workspace, void* stream) {
     if (!depth_est || !depth_gt || !depth_test || !frame || !frame_host || !K || !diameter || !taus || !err || !counts || !workspace) return GDRN_ERR_ARG;
     if (!vsd_shape_ok(N, H, W, T) || F <= 0 || (cost_type != GDRN_VSD_STEP && cost_type != GDRN_VSD_TLINEAR)) return GDRN_ERR_ARG;
-    if (!in_range(frame_host, N, F)) return GDRN_ERR_ARG;
+    if (!host_in_range(frame_host, N, F)) return GDRN_ERR_ARG;
     if (!vsd_shape_fits(N, H, W, T)) return GDRN_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int chunks = (int)vsd_chunks(H, W);
@@ -441,7 +420,7 @@ extern "C" int gdrn_mssd_mspd(const double* R_est, const double* t_est, const do
     if (!R_est || !t_est || !R_gt || !t_gt || !K || !labels || !labels_host || !pts || !npts || !sym_R || !sym_t || !nsym || !err || !workspace)
         return GDRN_ERR_ARG;
     if (N <= 0 || n_max <= 0 || S_max <= 0 || C <= 0) return GDRN_ERR_ARG;
-    if (!in_range(labels_host, N, C)) return GDRN_ERR_ARG;
+    if (!host_in_range(labels_host, N, C)) return GDRN_ERR_ARG;
     const int slabs = cdiv(S_max, MS_SLAB);
     if (N > 65535 || slabs > 65535 || cdiv(n_max, BM_THREADS) > 0x7fffffff / 2) return GDRN_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -465,7 +444,7 @@ extern "C" int gdrn_bop_recall_accumulate(const double* vsd_err, int T, const do
         !hits_mspd || !seen)
         return GDRN_ERR_ARG;
     if (N <= 0 || C <= 0 || T <= 0 || !(im_width > 0.0)) return GDRN_ERR_ARG;
-    if (!in_range(labels_host, N, C)) return GDRN_ERR_ARG;
+    if (!host_in_range(labels_host, N, C)) return GDRN_ERR_ARG;
     if (T > VSD_MAX_T) return GDRN_ERR_SHAPE;
     GDRN_LAUNCH(bop_recall_kernel, dim3(C), dim3(BM_THREADS), 0, reinterpret_cast<hipStream_t>(stream), vsd_err, T, mssd_mspd_err, labels, N,
                 diameter, 640.0 / im_width, ths_vsd, ths_mssd, ths_mspd, hits_vsd, hits_mssd, hits_mspd, seen);

@@ -15,6 +15,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 typedef unsigned short bf16_t;  // raw bits of the build's 16-bit format
 #ifdef GDRN_HALF_F16
 typedef __attribute__((ext_vector_type(8))) _Float16 bf16x8_t;
@@ -254,3 +257,22 @@ __device__ __forceinline__ void ranger_row(float* __restrict__ p, const float* _
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// compile-time loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>)
+template <class F, int... Is>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
+
+// LDS patch of the 3x3 kernels (conv3x3_halo.hip has the reasons): an even- and an odd-granule array of [pixel][4 granules + 16 B pad], so
+// HALF_PITCH bytes per pixel, the odd array a multiple of 256 B behind the even one.  half_bytes: the bytes of one such array of ppix pixels.
+constexpr int HALF_PITCH = 80;
+__host__ __device__ constexpr int half_bytes(int ppix) { return (ppix * HALF_PITCH + 255) / 256 * 256; }
+
+// one MFMA k-step on two 16-byte operand granules of T held as raw bits; T = bf16_t (the build's half) here, conv_gemm.hip adds fp32
+template <typename T>
+__device__ __forceinline__ f32x4_t mma_step(uint4 a, uint4 b, f32x4_t c);
+template <>
+__device__ __forceinline__ f32x4_t mma_step<bf16_t>(uint4 a, uint4 b, f32x4_t c) {
+    return GDRN_MFMA16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c);
+}

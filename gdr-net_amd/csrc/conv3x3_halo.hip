@@ -36,15 +36,7 @@ constexpr int ROWB = 128;   // bytes of K per stage row
 // (hardware lane groups); with one [pixel][8 granules] array those two sets collide on 7 of 8 banks whatever the pitch
 // (measured: SQ_LDS_BANK_CONFLICT = 45 % of the LDS cycles).  Even/odd k-groups in bank-aligned arrays make the two
 // sets land on the slots of DIFFERENT pixels -> conflict-free for every tap shift (16-pixel-wide tiles).
-constexpr int PITCH = 80;   // LDS pixel pitch inside one half array
-__host__ __device__ constexpr int half_bytes(int ppix) { return (ppix * PITCH + 255) / 256 * 256; }
-
-template <typename T>
-__device__ __forceinline__ f32x4_t mma_step(uint4 a, uint4 b, f32x4_t c);
-template <>
-__device__ __forceinline__ f32x4_t mma_step<bf16_t>(uint4 a, uint4 b, f32x4_t c) {
-    return GDRN_MFMA16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c);
-}
+// (HALF_PITCH and half_bytes, the size of one of the two arrays: common.h -- the stride-2 kernels and block64 share the layout)
 
 // fp32 (parity mode): a 16-byte operand granule = four k-steps of v_mfma_f32_16x16x4_f32 (lane group g supplies k = g of each); ks_ selects the
 // granule's float.  The four MFMAs of one granule pair are issued ACROSS the accumulator tuples (see MM below), not back to back on one.
@@ -196,7 +188,7 @@ __global__ __launch_bounds__(256 * KS, KS == 2 ? 1 : ((BN == 64 && TW == 16 && s
         const bool ok = inpatch && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi;
         const int iyc = min(max(iy, 0), p.Hi - 1), ixc = min(max(ix, 0), p.Wi - 1);
         poff[sj] = (unsigned)((n * p.Hi + iyc) * p.Wi + ixc) * (unsigned)p.x_cs * (unsigned)sizeof(T) + sg * 16;
-        pdst[sj] = inpatch ? (pp * PITCH + (sg & 1) * HB + (sg >> 1) * 16) : -1;
+        pdst[sj] = inpatch ? (pp * HALF_PITCH + (sg & 1) * HB + (sg >> 1) * 16) : -1;
         pokm |= ok ? (1u << sj) : 0u;
         if constexpr (XF != 0) {
             pinm |= (inpatch && py >= 1 && py <= TH && px >= 1 && px <= TW) ? (1u << sj) : 0u;
@@ -204,8 +196,8 @@ __global__ __launch_bounds__(256 * KS, KS == 2 ? 1 : ((BN == 64 && TW == 16 && s
         }
     }
     // PSLICE % 8 == 0 in the transform instantiations: the LDS slot of slice st is pdst0 + st * PDSTEP (no per-slice register)
-    constexpr int PDSTEP = (PSLICE / 8) * PITCH;
-    const int pdst0 = (tid >> 3) * PITCH + (tid & 1) * HB + ((tid & 7) >> 1) * 16 + grp * PDSTEP;
+    constexpr int PDSTEP = (PSLICE / 8) * HALF_PITCH;
+    const int pdst0 = (tid >> 3) * HALF_PITCH + (tid & 1) * HB + ((tid & 7) >> 1) * 16 + grp * PDSTEP;
     // slice st_ belongs to this thread's wave group / its index in the per-thread arrays and masks
 #define OWN(st_) (KS == 1 || (((st_) & 1) == grp))
 #define SJ(st_) (KS == 1 ? (st_) : ((st_) >> 1))
@@ -232,10 +224,10 @@ __global__ __launch_bounds__(256 * KS, KS == 2 ? 1 : ((BN == 64 && TW == 16 && s
 
     // ---- pixel-fragment lane base inside a patch: fragment b, lane column r16 -> pixel (oy, ox)
     int lbase;
-    if constexpr (TW == 16) lbase = r16 * PITCH + (g & 1) * HB + (g >> 1) * 16;                        // oy = b, ox = r16
-    else lbase = ((r16 >> 3) * PW + (r16 & 7)) * PITCH + (g & 1) * HB + (g >> 1) * 16;             // oy = 2b + (r16>>3)
+    if constexpr (TW == 16) lbase = r16 * HALF_PITCH + (g & 1) * HB + (g >> 1) * 16;                   // oy = b, ox = r16
+    else lbase = ((r16 >> 3) * PW + (r16 & 7)) * HALF_PITCH + (g & 1) * HB + (g >> 1) * 16;        // oy = 2b + (r16>>3)
     lbase += grp * 32;   // 8-wave form: the group's k-step of every stage
-    constexpr int FROW = (TW == 16) ? PW * PITCH : 2 * PW * PITCH;                    // byte step per fragment b
+    constexpr int FROW = (TW == 16) ? PW * HALF_PITCH : 2 * PW * HALF_PITCH;          // byte step per fragment b
 
     f32x4_t acc[FN][FM];
 #pragma unroll
@@ -299,7 +291,7 @@ __global__ __launch_bounds__(256 * KS, KS == 2 ? 1 : ((BN == 64 && TW == 16 && s
     uint4 fbA[FM], fbB[FM];
 #define RD(dst_, TAP_, KS_)                                                                                     \
     {                                                                                                           \
-        constexpr int tsh_ = ((TAP_) / 3) * PW * PITCH + ((TAP_) % 3) * PITCH;                                  \
+        constexpr int tsh_ = ((TAP_) / 3) * PW * HALF_PITCH + ((TAP_) % 3) * HALF_PITCH;                        \
         _Pragma("unroll") for (int b_ = 0; b_ < FM; ++b_)                                                       \
             dst_[b_] = *reinterpret_cast<const uint4*>(pcur + (b_ * FROW + tsh_ + (KS_) * 32));                 \
     }

@@ -50,11 +50,6 @@ __device__ __forceinline__ void dma16(const void* gbase, unsigned voff, unsigned
                  : "memory");
 }
 
-template <class F, int... Us>
-__device__ __forceinline__ void static_for_impl(F& f, std::integer_sequence<int, Us...>) { (f(std::integral_constant<int, Us>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
 #ifdef V3_DBG
 // bring-up instrumentation (tools/v3dbg.py builds this file alone with -DV3_DBG): cycle stamps per wave
 __device__ unsigned long long* g_v3_dbg;

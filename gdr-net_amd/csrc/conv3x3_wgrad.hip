@@ -43,12 +43,6 @@ template <> struct Geo<2> { static constexpr int TH = 4, KS = 1, PW = 17, PH = 9
 constexpr int XB = 153 * 144;            // X patch: 10x10 pixels x 160 B or 9x17 pixels x 144 B
 template <int NA> constexpr int stage_bytes() { return DyGeo<NA>::DYB + XB; }   // dY patch (up to 8x8 pixels) | X patch
 
-// compile-time loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>)
-template <class F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
 __device__ __forceinline__ bf16x8_t tr_pair(const unsigned char* p0, const unsigned char* p1) {
     bf16x4_t lo = GDRN_TR16((lds_bf16x4_t*)p0);
     bf16x4_t hi = GDRN_TR16((lds_bf16x4_t*)p1);

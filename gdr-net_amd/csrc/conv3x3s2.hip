@@ -8,7 +8,7 @@
 // through a three-tap register ring).  Its 9 x 33 input pixels of one 128-byte channel chunk live in LDS DE-INTERLEAVED BY PARITY: four planes
 // (even / odd input row) x (even / odd input column) of 5 x 17, 5 x 16, 4 x 17, 4 x 16 pixels.  Tap (ky, kx) of output pixel (oy, ox) reads
 // input (2 oy + ky - 1, 2 ox + kx - 1) = plane (ky & 1, kx & 1), row oy + (ky >> 1), column ox + (kx >> 1): a fragment of 16 output pixels of
-// one output row is 16 CONSECUTIVE pixels of one plane row -- the stride-1 kernel's conflict-free ds_read_b128 pattern (PITCH 80, even / odd
+// one output row is 16 CONSECUTIVE pixels of one plane row -- the stride-1 kernel's conflict-free ds_read_b128 pattern (HALF_PITCH 80, even / odd
 // granule arrays), every tap an immediate on one lane base.  The 1x1 shortcut reads exactly the centre tap's fragments (input (2 oy, 2 ox)):
 // eight more MFMAs per k-step into a second accumulator set, its row-major operand gathered from global memory (2 KiB per wave and chunk).
 // Epilogue = the halo kernel's fast path: per-tile BatchNorm statistics rows (train mode), or bias + ReLU (eval mode: folded BatchNorm).
@@ -22,19 +22,12 @@
 
 namespace {
 
-template <class F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
-constexpr int PITCH = 80;
-__host__ __device__ constexpr int half_bytes(int ppix) { return (ppix * PITCH + 255) / 256 * 256; }
 constexpr int TH = 4, BN = 128;
 constexpr int FM = TH, FN = 2;
 // Geometry of a pixel tile.  TW_ = 16: 4 x 16 output pixels of one image.  TW_ = 8 (maps 8 pixels wide: layer4.0, Patch-PnP's third conv): 4 x 8
 // output pixels of TWO images side by side -- a fragment's lanes 0-7 are a row of image 2 m, lanes 8-15 the same row of image 2 m + 1, whose
 // planes start IMG_OFF pixels further on.  IMG_OFF = 8 mod 16 pixels keeps the ds_read_b128 pattern conflict-free: the second half-row then
-// lands on the bank slots pixels 8-15 of a 16-pixel row would have (PITCH 80 B: 16 consecutive pixels cover the 64 banks once).
+// lands on the bank slots pixels 8-15 of a 16-pixel row would have (HALF_PITCH 80 B: 16 consecutive pixels cover the 64 banks once).
 template <int TW_>
 struct Geo {
     static constexpr int TW = TW_, NI = 16 / TW_;                  // images per tile
@@ -54,10 +47,6 @@ struct Geo {
     }
 };
 static_assert(Geo<8>::IMG_OFF % 16 == 8 && Geo<8>::IMG_OFF >= Geo<8>::IPIX, "second image's planes: 8 mod 16 pixels behind the first's");
-
-__device__ __forceinline__ f32x4_t mma(uint4 a, uint4 b, f32x4_t c) {
-    return GDRN_MFMA16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c);
-}
 
 // BNB (r6b, with !DS): the launch is a DATA GRADIENT -- the head's ConvTranspose2d backward is a stride-2 conv of the output gradient -- w.r.t. the
 // output of a BatchNorm(+ReLU): ReLU mask (stored activation > 0) and that BatchNorm's two backward sums on the accumulators, one partial row per
@@ -113,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_kernel(const gdrn_s2_params 
         const bool ok = in && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi;
         const int iyc = min(max(iy, 0), p.Hi - 1), ixc = min(max(ix, 0), p.Wi - 1);
         poff[i] = (unsigned)(((n + min(img, NI - 1)) * p.Hi + iyc) * p.Wi + ixc) * (unsigned)p.x_cs * 2u + sg * 16;
-        pdst[i] = in ? ((img * G::IMG_OFF + q) * PITCH + (sg & 1) * HB + (sg >> 1) * 16) : -1;
+        pdst[i] = in ? ((img * G::IMG_OFF + q) * HALF_PITCH + (sg & 1) * HB + (sg >> 1) * 16) : -1;
         pokm |= ok ? (1u << i) : 0u;
     }
     const char* xg = reinterpret_cast<const char*>(p.x);
@@ -134,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_kernel(const gdrn_s2_params 
     const char* wdl = nullptr;
     if constexpr (DS) wdl = reinterpret_cast<const char*>(p.wd) + ((size_t)(co0 + wave * 32 + (r16 >> 2) * 8 + (r16 & 3)) * p.Cin + g * 8) * 2;
 
-    const int lb = ((r16 / TW) * G::IMG_OFF + (r16 % TW)) * PITCH + (g & 1) * HB + (g >> 1) * 16;
+    const int lb = ((r16 / TW) * G::IMG_OFF + (r16 % TW)) * HALF_PITCH + (g & 1) * HB + (g >> 1) * 16;
     f32x4_t acc[FN][FM], accd[DS ? FN : 1][DS ? FM : 1];
 #pragma unroll
     for (int a = 0; a < FN; ++a)
@@ -149,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_kernel(const gdrn_s2_params 
     auto rd = [&](uint4 (&dst)[FM], auto S_) {
         constexpr int s_ = decltype(S_)::value, tap = s_ / 2, ks = s_ % 2;
 #pragma unroll
-        for (int b = 0; b < FM; ++b) dst[b] = *reinterpret_cast<const uint4*>(smem + lb + G::template tap_pix<tap>(b) * PITCH + ks * 32);
+        for (int b = 0; b < FM; ++b) dst[b] = *reinterpret_cast<const uint4*>(smem + lb + G::template tap_pix<tap>(b) * HALF_PITCH + ks * 32);
     };
     for (int kc = 0; kc < kch; ++kc) {
         const bool more = kc + 1 < kch;
@@ -175,12 +164,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_kernel(const gdrn_s2_params 
 #pragma unroll
             for (int a = 0; a < FN; ++a)
 #pragma unroll
-                for (int b = 0; b < FM; ++b) acc[a][b] = mma(wq[a * 2 + ks], src[b], acc[a][b]);
+                for (int b = 0; b < FM; ++b) acc[a][b] = mma_step<bf16_t>(wq[a * 2 + ks], src[b], acc[a][b]);
             if constexpr (DS && tap == 4) {
 #pragma unroll
                 for (int a = 0; a < FN; ++a)
 #pragma unroll
-                    for (int b = 0; b < FM; ++b) accd[a][b] = mma(wdq[a * 2 + ks], src[b], accd[a][b]);
+                    for (int b = 0; b < FM; ++b) accd[a][b] = mma_step<bf16_t>(wdq[a * 2 + ks], src[b], accd[a][b]);
             }
             if constexpr (ks == 1) {   // the tap is done: its ring slot takes the weights three taps ahead (the next chunk's behind tap 5)
                 constexpr int ntap = (tap + 3) % 9;

@@ -9,7 +9,7 @@
 // the input pixels fall into four parity classes (iy & 1, ix & 1) with 1 / 2 / 2 / 4 taps, and every one of the nine (tap, class) products reads
 // dY at (a + da, b + db), da, db in {0, 1}, where (a, b) = (iy >> 1, ix >> 1).  A workgroup (4 waves, wave w = 16 of the workgroup's 64 dX
 // channels) owns a 4 x 16 block of (a, b) = an 8 x 32 tile of dX, stages the 5 x 17 dY pixels of one 128-byte channel chunk in LDS (the
-// stride-1 halo kernel's layout: fragments of 16 consecutive pixels, PITCH 80, even / odd granule arrays) and keeps FOUR accumulator sets,
+// stride-1 halo kernel's layout: fragments of 16 consecutive pixels, HALF_PITCH 80, even / odd granule arrays) and keeps FOUR accumulator sets,
 // one per class.  Per k-step: 4 shifted fragment sets (16 ds_read_b128) feed 36 MFMAs -- the four sets are the pipeline's stages (the next
 // set's reads and weight blocks go out in front of the current set's MFMAs).  Weights: the fragment-major operand of gdrn_pack_wfrag of the
 // data-gradient operand [Cin rows][9 taps, not flipped][Cout], streamed L2 -> VGPR.
@@ -27,13 +27,6 @@
 
 namespace {
 
-template <class F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
-constexpr int PITCH = 80;
-__host__ __device__ constexpr int half_bytes(int ppix) { return (ppix * PITCH + 255) / 256 * 256; }
 constexpr int TH = 4, BNC = 64;                             // (a, b) block rows; dX channels per workgroup
 constexpr int FM = TH;
 template <int TW_>
@@ -47,10 +40,6 @@ struct Geo {
     static constexpr int NS1 = (NI * IPIX * 8 + 255) / 256, NS2 = NI * I2PIX * 8 / 256;   // patch granules per thread: 3 + 2
 };
 static_assert(Geo<8>::IMG_OFF % 16 == 8 && Geo<8>::IMG_OFF2 % 16 == 8, "second image: 8 mod 16 pixels behind the first");
-
-__device__ __forceinline__ f32x4_t mma(uint4 a, uint4 b, f32x4_t c) {
-    return GDRN_MFMA16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c);
-}
 
 // the four fragment sets (da, db) of a k-step and the (tap, class) products that read them; class = (iy & 1) * 2 + (ix & 1)
 // set 0 = (da, db) = (0, 0): taps (ky, kx) = (1,1) (1,2) (2,1) (2,2) -> classes 0 1 2 3;  set 1 = (0, 1): (1,0) (2,0) -> 1 3;
@@ -112,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad_kernel(const gdrn_s2d_
         const int oy = y0 + pa, ox = x0 + pb;
         const bool in = qq < NI * IPIX, ok = in && oy < p.Ho && ox < p.Wo;
         poff[i] = (unsigned)(((n + min(img, NI - 1)) * p.Ho + min(oy, p.Ho - 1)) * p.Wo + min(ox, p.Wo - 1)) * (unsigned)p.dy_cs * 2u + sg * 16;
-        pdst[i] = in ? ((img * G::IMG_OFF + q) * PITCH + (sg & 1) * HB + (sg >> 1) * 16) : -1;
+        pdst[i] = in ? ((img * G::IMG_OFF + q) * HALF_PITCH + (sg & 1) * HB + (sg >> 1) * 16) : -1;
         pokm |= ok ? (1u << i) : 0u;
     }
     if constexpr (DS) {
@@ -121,7 +110,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad_kernel(const gdrn_s2d_
             const int id = i * 256 + tid, qq = id >> 3, sg = id & 7;
             const int img = NI == 1 ? 0 : qq / G::I2PIX, q = qq - img * G::I2PIX;
             poff2[i] = (unsigned)(((n + img) * p.Ho + y0 + q / TW) * p.Wo + x0 + (q % TW)) * (unsigned)p.dyd_cs * 2u + sg * 16;
-            pdst2[i] = (img * G::IMG_OFF2 + q) * PITCH + (sg & 1) * HB2 + (sg >> 1) * 16;
+            pdst2[i] = (img * G::IMG_OFF2 + q) * HALF_PITCH + (sg & 1) * HB2 + (sg >> 1) * 16;
         }
     }
     const char* yg = reinterpret_cast<const char*>(p.dy);
@@ -165,8 +154,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad_kernel(const gdrn_s2d_
     }
 
     const int limg = r16 / TW, lcol = r16 % TW;   // image of the tile / column of the (a, b) block this lane's fragment pixel belongs to
-    const int lb = (limg * G::IMG_OFF + lcol) * PITCH + (g & 1) * HB + (g >> 1) * 16;
-    const int lb2 = (limg * G::IMG_OFF2 + lcol) * PITCH + (g & 1) * HB2 + (g >> 1) * 16;
+    const int lb = (limg * G::IMG_OFF + lcol) * HALF_PITCH + (g & 1) * HB + (g >> 1) * 16;
+    const int lb2 = (limg * G::IMG_OFF2 + lcol) * HALF_PITCH + (g & 1) * HB2 + (g >> 1) * 16;
     f32x4_t acc[4][FM];
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -182,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad_kernel(const gdrn_s2d_
         constexpr int s_ = decltype(S_)::value, ks = s_ >> 2;
         using Q = SetOf<(s_ & 3)>;
 #pragma unroll
-        for (int b = 0; b < FM; ++b) dst[b] = *reinterpret_cast<const uint4*>(scur + lb + ((b + Q::da) * PW + Q::db) * PITCH + ks * 32);
+        for (int b = 0; b < FM; ++b) dst[b] = *reinterpret_cast<const uint4*>(scur + lb + ((b + Q::da) * PW + Q::db) * HALF_PITCH + ks * 32);
     };
     auto ldw = [&](uint4 (&dst)[4], int kc, auto S_) {
         constexpr int s_ = decltype(S_)::value, ks = s_ >> 2;
@@ -227,8 +216,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad_kernel(const gdrn_s2d_
             for (int i = 0; i < Q::n; ++i)
 #pragma unroll
                 for (int b = 0; b < FM; ++b) {
-                    if constexpr (WD) acc[set_cls(s_ & 3, i)][b] = mma(wc[ks * 9 + SETBASE[s_ & 3] + i], src[b], acc[set_cls(s_ & 3, i)][b]);
-                    else acc[set_cls(s_ & 3, i)][b] = mma(wq[i], src[b], acc[set_cls(s_ & 3, i)][b]);
+                    if constexpr (WD) acc[set_cls(s_ & 3, i)][b] = mma_step<bf16_t>(wc[ks * 9 + SETBASE[s_ & 3] + i], src[b], acc[set_cls(s_ & 3, i)][b]);
+                    else acc[set_cls(s_ & 3, i)][b] = mma_step<bf16_t>(wq[i], src[b], acc[set_cls(s_ & 3, i)][b]);
                 }
             if constexpr (WD) {   // the stage's blocks are consumed: the next chunk's go into the same registers
                 if (more) {
@@ -239,8 +228,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad_kernel(const gdrn_s2d_
             if constexpr (DS && (s_ & 3) == 3) {   // the 1x1 shortcut's gradient: even / even pixels only, its own (unshifted) fragments
 #pragma unroll
                 for (int b = 0; b < FM; ++b) {
-                    const uint4 f2 = *reinterpret_cast<const uint4*>(scur + PBYTES + lb2 + b * TW * PITCH + ks * 32);
-                    acc[0][b] = mma(wdq[ks], f2, acc[0][b]);
+                    const uint4 f2 = *reinterpret_cast<const uint4*>(scur + PBYTES + lb2 + b * TW * HALF_PITCH + ks * 32);
+                    acc[0][b] = mma_step<bf16_t>(wdq[ks], f2, acc[0][b]);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);

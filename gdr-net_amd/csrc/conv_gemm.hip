@@ -18,18 +18,6 @@
 #include "common.h"
 #include "../../include/gdrn_hip.h"
 
-namespace {
-
-constexpr int ROWB = 128;  // bytes of K per LDS row per stage
-
-template <typename T>
-__device__ __forceinline__ f32x4_t mma_step(uint4 a, uint4 b, f32x4_t c);
-
-template <>
-__device__ __forceinline__ f32x4_t mma_step<bf16_t>(uint4 a, uint4 b, f32x4_t c) {
-    return GDRN_MFMA16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c);
-}
-
 template <>
 __device__ __forceinline__ f32x4_t mma_step<float>(uint4 a, uint4 b, f32x4_t c) {
     // lane group g holds k = 4g..4g+3 of this 16-wide k-step for BOTH operands; the four MFMAs below
@@ -40,6 +28,10 @@ __device__ __forceinline__ f32x4_t mma_step<float>(uint4 a, uint4 b, f32x4_t c) 
     c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
     return c;
 }
+
+namespace {
+
+constexpr int ROWB = 128;  // bytes of K per LDS row per stage
 
 template <typename T, int BM, int BN>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 && BM == 64 && BN == 128) ? 3 : 2) void conv_gemm_kernel(const gdrn_conv_params p) {

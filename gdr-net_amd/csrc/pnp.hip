@@ -13,6 +13,7 @@
 // This is not cv2's algorithm (EPnP, its own RNG and a 0.99-confidence early stop): results are pinned to geometry, not to cv2 output.
 // (The file has no 16-bit code: both library builds compile the same thing.)
 #include "common.h"
+#include "geom64.h"
 #include "../../include/gdrn_hip.h"
 
 namespace {
@@ -90,9 +91,8 @@ PNP_HD bool pnp_project(const double* K, const double* Xc, double* u, double* v)
 }
 
 PNP_HD void pnp_xform(const double* R, const double* t, const double* X, double* Xc) {
-    Xc[0] = fma(R[0], X[0], fma(R[1], X[1], fma(R[2], X[2], t[0])));
-    Xc[1] = fma(R[3], X[0], fma(R[4], X[1], fma(R[5], X[2], t[1])));
-    Xc[2] = fma(R[6], X[0], fma(R[7], X[1], fma(R[8], X[2], t[2])));
+    const V3 c = xform(R, t, load3(X));
+    Xc[0] = c.x, Xc[1] = c.y, Xc[2] = c.z;
 }
 
 // squared reprojection error [px^2] of one correspondence, +inf behind the camera (NaN stays NaN: every comparison with it is false)
@@ -364,12 +364,6 @@ PNP_HD void pnp_accumulate(const double* K, const double* R, const double* t, co
     acc[27] += ru * ru + rv * rv;
 }
 
-__device__ __forceinline__ double pnp_wave_sum(double v) {   // xor tree: a fixed order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // the workgroup's LDS of the refinement kernel
 struct PnpRefineLds {
     double red[4][28];
@@ -388,7 +382,7 @@ __device__ __forceinline__ void pnp_block_sum28(const double* acc, PnpRefineLds&
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 28; ++k) {
-        const double s = pnp_wave_sum(acc[k]);
+        const double s = wave_sum_f64(acc[k]);
         if (lane == 0) L.red[wave][k] = s;
     }
     __syncthreads();

@@ -9,6 +9,7 @@
 // on these numbers.  No floating-point atomics: per-workgroup partial sums go to a caller-owned workspace and are added up in a fixed order,
 // two runs give the same bits.  (The file has no 16-bit code: both library builds compile the same thing.)
 #include "common.h"
+#include "geom64.h"
 #include "../../include/gdrn_hip.h"
 
 namespace {
@@ -19,18 +20,6 @@ constexpr int PM_SLAB = PM_THREADS * PM_G;     // points of one workgroup
 constexpr int PM_TILE = 512;                   // estimate-posed points per LDS tile (3 x 4 KiB)
 constexpr int PM_FLAGS = 15;
 
-struct V3 { double x, y, z; };
-
-// R p + t.  Explicit fma chains: the same operations at every call site, whatever the compiler would contract -- a point posed on its way into
-// LDS and the same point posed into a register are the same bits, so an estimate equal to the ground truth scores exactly 0, as in the reference.
-__device__ __forceinline__ V3 xform(const double* R, const double* t, V3 p) {
-    V3 o;
-    o.x = fma(R[0], p.x, fma(R[1], p.y, fma(R[2], p.z, t[0])));
-    o.y = fma(R[3], p.x, fma(R[4], p.y, fma(R[5], p.z, t[1])));
-    o.z = fma(R[6], p.x, fma(R[7], p.y, fma(R[8], p.z, t[2])));
-    return o;
-}
-
 // pose_error.py:400-415: rad2deg(arccos(clamp(0.5 (min(tr(A B^T), 3) - 1), -1, 1)))
 __device__ __forceinline__ double re_deg(const double* A, const double* B) {
     double tr = 0.0;
@@ -39,21 +28,6 @@ __device__ __forceinline__ double re_deg(const double* A, const double* B) {
     tr = tr <= 3.0 ? tr : 3.0;
     const double c = fmin(1.0, fmax(-1.0, 0.5 * (tr - 1.0)));
     return acos(c) * (180.0 / 3.14159265358979323846);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {   // xor tree: a fixed order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// block-wide sum for 256-thread blocks in a fixed order; result valid in every thread.  `red` is >= 4 doubles of LDS.
-__device__ __forceinline__ double block_sum_256_f64(double v, double* red) {
-    v = wave_sum_f64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // One thread per row: te, the closest ground-truth rotation (kept in rsel[row][9] for the point kernel) and re.
@@ -145,7 +119,7 @@ __global__ __launch_bounds__(PM_THREADS) void pose_points_kernel(const double* _
         const int idx = base + u * PM_THREADS + tid;
         valid[u] = idx < n;
         V3 p = {0.0, 0.0, 0.0};
-        if (valid[u]) { p.x = P[(size_t)idx * 3 + 0]; p.y = P[(size_t)idx * 3 + 1]; p.z = P[(size_t)idx * 3 + 2]; }
+        if (valid[u]) p = load3(P + (size_t)idx * 3);
         const V3 pe = xform(Re, te, p);
         g[u] = xform(Rg, tg, p);
         const V3 ps = xform(Rs, tg, p);
@@ -168,9 +142,7 @@ __global__ __launch_bounds__(PM_THREADS) void pose_points_kernel(const double* _
             const int cnt = min(PM_TILE, n - t0);
             __syncthreads();   // the previous tile has been consumed
             for (int j = tid; j < cnt; j += PM_THREADS) {
-                const size_t idx = (size_t)(t0 + j) * 3;
-                const V3 p = {P[idx + 0], P[idx + 1], P[idx + 2]};
-                const V3 pe = xform(Re, te, p);
+                const V3 pe = xform(Re, te, load3(P + (size_t)(t0 + j) * 3));
                 sx[j] = pe.x;
                 sy[j] = pe.y;
                 sz[j] = pe.z;
@@ -257,12 +229,6 @@ __global__ __launch_bounds__(PM_THREADS) void pose_recall_kernel(const double* _
     }
 }
 
-int labels_ok(const int* labels_host, int N, int C) {
-    for (int i = 0; i < N; ++i)
-        if (labels_host[i] < 0 || labels_host[i] >= C) return 0;
-    return 1;
-}
-
 }  // namespace
 
 extern "C" long long gdrn_pose_metrics_workspace_bytes(int N, int n_max) {
@@ -277,7 +243,7 @@ extern "C" int gdrn_pose_errors(const double* R_est, const double* t_est, const 
                                 void* stream) {
     if (!R_est || !t_est || !R_gt || !t_gt || !K || !labels || !labels_host || !pts || !npts || !is_sym || !err || !workspace) return GDRN_ERR_ARG;
     if (N <= 0 || n_max <= 0 || C <= 0 || Kmax < 0 || (Kmax > 0 && (!sym || !nsym))) return GDRN_ERR_ARG;
-    if (!labels_ok(labels_host, N, C)) return GDRN_ERR_ARG;
+    if (!host_in_range(labels_host, N, C)) return GDRN_ERR_ARG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int slabs = cdiv(n_max, PM_SLAB);
     double* rsel = reinterpret_cast<double*>(workspace);
@@ -297,7 +263,7 @@ extern "C" int gdrn_pose_recall_accumulate(const double* err, const int* labels,
                                            long long* hits, long long* seen, double* re_sum, double* te_sum, long long* err_cnt,
                                            void* stream) {
     if (!err || !labels || !labels_host || !diameter || !hits || !seen || !re_sum || !te_sum || !err_cnt || N <= 0 || C <= 0) return GDRN_ERR_ARG;
-    if (!labels_ok(labels_host, N, C)) return GDRN_ERR_ARG;
+    if (!host_in_range(labels_host, N, C)) return GDRN_ERR_ARG;
     GDRN_LAUNCH(pose_recall_kernel, dim3(C), dim3(PM_THREADS), 0, reinterpret_cast<hipStream_t>(stream), err, labels, N, diameter, hits, seen,
                 re_sum, te_sum, err_cnt);
     GDRN_CHECK_LAUNCH();

@@ -11,6 +11,7 @@
 // operation sequence on (ray, the edge's two camera-space vertices in ascending index order), whichever code path, triangle or launch shape
 // evaluates it -- the watertightness and order-independence guarantees rest on that.  (No 16-bit code: both library builds compile the same thing.)
 #include "common.h"
+#include "geom64.h"
 #include "../../include/gdrn_hip.h"
 
 #pragma clang fp contract(off)
@@ -23,8 +24,6 @@ constexpr int RD_SMALL = 64;                    // screen boxes of up to this ma
 constexpr unsigned RD_INF_BITS = 0x7f800000u;   // +inf: the cleared depth buffer
 constexpr int RD_MAX_SPLIT = 16;
 constexpr int RD_TARGET_WGS = 1024;             // (4 per CU) below this many workgroups the tile walk of the large triangles is split further
-
-struct V3 { double x, y, z; };
 
 struct Cam { double fx, sk, cx, fy, cy; };      // K = [[fx, sk, cx], [0, fy, cy], [0, 0, 1]]
 
@@ -39,15 +38,6 @@ __device__ __forceinline__ Cam load_cam(const double* K) { return Cam{K[0], K[1]
 
 __device__ __forceinline__ V3 cross(V3 p, V3 q) {
     return V3{p.y * q.z - p.z * q.y, p.z * q.x - p.x * q.z, p.x * q.y - p.y * q.x};
-}
-
-// R v + t
-__device__ __forceinline__ V3 to_cam(const double* R, const double* t, const double* v) {
-    V3 o;
-    o.x = fma(R[0], v[0], fma(R[1], v[1], fma(R[2], v[2], t[0])));
-    o.y = fma(R[3], v[0], fma(R[4], v[1], fma(R[5], v[2], t[1])));
-    o.z = fma(R[6], v[0], fma(R[7], v[1], fma(R[8], v[2], t[2])));
-    return o;
 }
 
 // the ray of pixel (x, y): K^-1 [x, y, 1] for the upper-triangular K, third component exactly 1
@@ -123,7 +113,7 @@ __global__ __launch_bounds__(RD_THREADS) void render_raster_kernel(const double*
         if (ia > ib) { tmp = ia; ia = ib; ib = tmp; }
         if (ia >= 0 && ic < nv) {   // (MeshTable range-checks the indices on the host)
             const double* vb = verts + (size_t)vert_off[c] * 3;
-            const V3 a = to_cam(R, t, vb + (size_t)ia * 3), b = to_cam(R, t, vb + (size_t)ib * 3), cc = to_cam(R, t, vb + (size_t)ic * 3);
+            const V3 a = xform(R, t, load3(vb + (size_t)ia * 3)), b = xform(R, t, load3(vb + (size_t)ib * 3)), cc = xform(R, t, load3(vb + (size_t)ic * 3));
             if (a.z >= near && b.z >= near && cc.z >= near) {   // a vertex in front of the near plane drops the whole triangle (no clipping)
                 const V3 ab = {b.x - a.x, b.y - a.y, b.z - a.z}, ac = {cc.x - a.x, cc.y - a.y, cc.z - a.z};
                 const V3 n = cross(ab, ac);
@@ -272,8 +262,7 @@ extern "C" int gdrn_render_depth(const double* verts, const int* faces, const in
                                  const double* t, const double* K, int N, int H, int W, double near, double far, float* depth, void* stream) {
     if (!verts || !faces || !vert_off || !nverts || !face_off || !nfaces || !labels || !labels_host || !R || !t || !K || !depth) return GDRN_ERR_ARG;
     if (!frame_ok(N, H, W) || C <= 0 || f_max <= 0 || !(near > 0.0) || !(near < far)) return GDRN_ERR_ARG;
-    for (int i = 0; i < N; ++i)
-        if (labels_host[i] < 0 || labels_host[i] >= C) return GDRN_ERR_ARG;
+    if (!host_in_range(labels_host, N, C)) return GDRN_ERR_ARG;
     const int chunks = cdiv(f_max, RD_THREADS);
     if (!frame_fits(N, H, W) || chunks > 65535) return GDRN_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

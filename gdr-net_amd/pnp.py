@@ -11,16 +11,11 @@ is fp64.  This is NOT cv2's algorithm: a fixed hypothesis count instead of the 0
 of EPnP, a counter-based hash instead of cv2's RNG -- the results are pinned to geometry (known poses) and to an independent fp64 host
 computation, not to cv2 output.  There is no CPU fallback.
 """
-import numpy as np
 import torch
 
-from . import cabi, postproc
+from . import cabi, devargs, postproc
 
-
-def _dev(t, what):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise cabi.GdrnHipError(f"PnP runs on the GPU (no CPU fallback): {what} is not a device tensor")
-    return t.detach()
+WHERE = "PnP"   # (this module in devargs' error sentence)
 
 
 def _inputs(image_points, model_points, counts, K):
@@ -28,35 +23,19 @@ def _inputs(image_points, model_points, counts, K):
     (checked against the stride on the host, before anything is loaded or launched) and K [N,3,3] fp64"""
     for name, v in (("image_points", image_points), ("model_points", model_points), ("K", K)):
         if not isinstance(v, torch.Tensor):
-            raise cabi.GdrnHipError(f"PnP runs on the GPU (no CPU fallback): {name} is not a device tensor")
+            raise devargs.no_fallback(name, WHERE)
     img, mod = image_points.detach(), model_points.detach()
     if img.dim() != 3 or mod.dim() != 3 or img.shape[2] != 2 or mod.shape[2] != 3 or img.shape[:2] != mod.shape[:2]:
         raise ValueError(f"image_points [N,S,2] and model_points [N,S,3] expected, got {tuple(img.shape)} and {tuple(mod.shape)}")
     N, S = int(img.shape[0]), int(img.shape[1])
     if N <= 0 or S <= 0:
         raise ValueError("empty batch")
-    if isinstance(counts, torch.Tensor):
-        host = counts.detach().cpu().numpy()
-    else:
-        host = np.asarray(counts)
-    host = np.ascontiguousarray(host.reshape(-1).astype(np.int32))
-    if host.shape[0] != N:
-        raise ValueError(f"{host.shape[0]} counts for {N} RoIs")
-    if (host < 0).any() or (host > S).any():
-        raise ValueError(f"counts outside [0, {S}]")
-    K = K.detach().to(torch.float64).reshape(-1, 3, 3)
-    if K.shape[0] == 1 and N > 1:
-        K = K.expand(N, 3, 3)
-    if K.shape[0] != N:
-        raise ValueError(f"{K.shape[0]} camera matrices for {N} RoIs")
-    _dev(img, "image_points"), _dev(mod, "model_points"), _dev(K, "K")   # (after the checks that need no device: a bad call fails the same everywhere)
+    cnt, host = devargs.index_vector(counts, N, S, img.device, "counts", inclusive=True)
+    K = devargs.per_row_K(K.detach().to(torch.float64), N)
     dt = torch.float64 if img.dtype == torch.float64 and mod.dtype == torch.float64 else torch.float32
-    img, mod = img.to(dt).contiguous(), mod.to(dt).contiguous()
-    if isinstance(counts, torch.Tensor) and counts.device.type == "cuda":
-        cnt = counts.detach().reshape(-1).to(torch.int32).contiguous()
-    else:
-        cnt = torch.from_numpy(host).to(img.device)
-    return img, mod, cnt, host, K.contiguous(), N, S, dt == torch.float64
+    # (after the checks that need no device: a bad call fails the same everywhere)
+    img, mod = devargs.device_tensor(img, dt, None, "image_points", WHERE), devargs.device_tensor(mod, dt, None, "model_points", WHERE)
+    return img, mod, cnt, host, devargs.device_tensor(K, None, None, "K", WHERE), N, S, dt == torch.float64
 
 
 def _pose0(R0, t0, N, dev):
@@ -64,14 +43,14 @@ def _pose0(R0, t0, N, dev):
     if R0 is None:
         R = torch.eye(3, dtype=torch.float64, device=dev).repeat(N, 1, 1)
     else:
-        R = _dev(R0, "R0").to(torch.float64).reshape(-1, 3, 3).clone()
+        R = devargs.device_tensor(R0, torch.float64, (-1, 3, 3), "R0", WHERE).clone()
     if t0 is None:
         t = torch.zeros(N, 3, dtype=torch.float64, device=dev)
     else:
-        t = _dev(t0, "t0").to(torch.float64).reshape(-1, 3).clone()
+        t = devargs.device_tensor(t0, torch.float64, (-1, 3), "t0", WHERE).clone()
     if R.shape[0] != N or t.shape[0] != N:
         raise ValueError(f"R0 / t0 need one entry per RoI ({N})")
-    return R.contiguous(), t.contiguous()
+    return R, t
 
 
 def pnp_ransac(image_points, model_points, counts, K, reproj_err=3.0, iters=100, seed=0, R0=None, t0=None, want_mask=False, max_iter=20):
@@ -90,8 +69,8 @@ def pnp_ransac(image_points, model_points, counts, K, reproj_err=3.0, iters=100,
     num = torch.empty(N, dtype=torch.int32, device=dev)
     rms = torch.empty(N, dtype=torch.float64, device=dev)
     mask = torch.empty(N, S, dtype=torch.uint8, device=dev) if want_mask else None
-    ws = torch.empty(int(lib.gdrn_pnp_workspace_bytes(N, S, int(iters))), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    ws = devargs.workspace(lib.gdrn_pnp_workspace_bytes(N, S, int(iters)), dev, "pnp_workspace_bytes")
+    st = devargs.stream(dev)
     fn = lib.gdrn_pnp_ransac_f64 if f64 else lib.gdrn_pnp_ransac
     cabi.check(fn(cabi.ptr(img), cabi.ptr(mod), cabi.ptr(cnt), host.ctypes.data, cabi.ptr(K), N, S, float(reproj_err), int(iters),
                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iter), cabi.ptr(R), cabi.ptr(t), cabi.ptr(ok), cabi.ptr(num), cabi.ptr(mask), cabi.ptr(rms),
@@ -113,7 +92,7 @@ def pnp_refine(image_points, model_points, counts, K, R0, t0, max_iter=20):
     lib = cabi.load()
     ok = torch.empty(N, dtype=torch.int32, device=dev)
     rms = torch.empty(N, dtype=torch.float64, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = devargs.stream(dev)
     fn = lib.gdrn_pnp_refine_f64 if f64 else lib.gdrn_pnp_refine
     cabi.check(fn(cabi.ptr(img), cabi.ptr(mod), cabi.ptr(cnt), host.ctypes.data, cabi.ptr(K), N, S, int(max_iter), cabi.ptr(R), cabi.ptr(t),
                   cabi.ptr(ok), cabi.ptr(rms), None, st), "pnp_refine")
@@ -138,13 +117,13 @@ def poses_from_maps(cfg, out_dict, roi_coord_2d, roi_extents, im_H, im_W, K, pnp
         raise NotImplementedError(f"unknown pnp type on the MI355X path: {kind}")
     _, _, img, mod, counts = postproc.get_img_model_points_with_coords2d(cfg, out_dict, roi_coord_2d, roi_extents, im_H, im_W)
     N, dev = img.shape[0], img.device
-    K = _dev(torch.as_tensor(K) if not isinstance(K, torch.Tensor) else K, "K")
+    K = devargs.device_tensor(torch.as_tensor(K), None, None, "K", WHERE)
     if kind == "ransac_pnp":
         res = pnp_ransac(img, mod, counts, K, reproj_err=3.0, iters=100, seed=seed)
         pose = torch.cat([res["R"], res["t"].unsqueeze(2)], dim=2)
         return torch.where(res["ok"].bool().view(N, 1, 1), pose, torch.full_like(pose, -100.0))
-    R_net = _dev(out_dict["rot"], "rot").to(torch.float64).reshape(N, 3, 3)
-    t_net = _dev(out_dict["trans"], "trans").to(torch.float64).reshape(N, 3)
+    R_net = devargs.device_tensor(out_dict["rot"], torch.float64, (N, 3, 3), "rot", WHERE)
+    t_net = devargs.device_tensor(out_dict["trans"], torch.float64, (N, 3), "trans", WHERE)
     if kind == "net_ransac_pnp":
         res = pnp_ransac(img, mod, counts, K, reproj_err=3.0, iters=20, seed=seed, R0=R_net, t0=t_net)
     else:

@@ -14,31 +14,28 @@ instance).  ``pose_errors`` returns device tensors; ``PoseRecall`` keeps its cou
 import numpy as np
 import torch
 
-from . import cabi
+from . import cabi, devargs
 
 ERROR_NAMES = ("ad", "re", "te", "proj")
 METRIC_NAMES = ("ad_2", "ad_5", "ad_10", "rete_2", "rete_5", "rete_10", "re_2", "re_5", "re_10", "te_2", "te_5", "te_10",
                 "proj_2", "proj_5", "proj_10")   # the evaluator's order (:516-532) = the column order of the kernel's hits
+WHERE = "the pose metrics"   # (this module in devargs' error sentence)
 
 
-class ModelTable:
+class ModelTable(devargs.DeviceTables):
     """Per-class model tables, packed once: ``points`` a list of [n_c,3] arrays, ``diameters`` [C], ``sym_infos`` None or per class None / [K,3,3]
     (a bare 3x3 is one symmetry, as get_closest_rot reshapes it), ``sym_classes`` the class indices scored as symmetric (the role of
     cfg.DATASETS.SYM_OBJS: adi instead of add, closest-rotation search).  ``pad_value`` fills the table rows beyond a class's own points; the
     kernels never read them into a result."""
 
+    TABLES = ("pts", "npts", "diameter", "sym", "nsym", "is_sym")
+
     def __init__(self, points, diameters, sym_infos=None, sym_classes=(), pad_value=0.0):
         C = len(points)
         if C == 0 or len(diameters) != C or (sym_infos is not None and len(sym_infos) != C):
             raise ValueError("points, diameters and sym_infos need one entry per class")
-        pts = [np.asarray(p, dtype=np.float64).reshape(-1, 3) for p in points]
         self.num_classes = C
-        self.npts = np.array([len(p) for p in pts], dtype=np.int32)
-        self.n_max = max(1, int(self.npts.max()))
-        self.pts = np.full((C, self.n_max, 3), float(pad_value), dtype=np.float64)
-        for c, p in enumerate(pts):
-            self.pts[c, : len(p)] = p
-        self.diameter = np.asarray(diameters, dtype=np.float64).reshape(C).copy()
+        self.pts, self.npts, self.n_max, self.diameter = devargs.pack_points(points, diameters, pad_value, n_min=1)   # (a class may be empty)
         syms = [None] * C if sym_infos is None else [None if s is None else np.asarray(s, dtype=np.float64).reshape(-1, 3, 3) for s in sym_infos]
         self.nsym = np.array([0 if s is None else len(s) for s in syms], dtype=np.int32)
         self.k_max = max(1, int(self.nsym.max()))
@@ -51,56 +48,22 @@ class ModelTable:
             if not 0 <= int(c) < C:
                 raise ValueError(f"sym_classes: {c} is not a class index below {C}")
             self.is_sym[int(c)] = 1
-        self._dev = {}
-
-    def on(self, device):
-        """the tables as device tensors (uploaded once per device)."""
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = {k: torch.from_numpy(getattr(self, k)).to(device) for k in ("pts", "npts", "diameter", "sym", "nsym", "is_sym")}
-        return self._dev[key]
-
-
-def _f64(t, shape, what):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise cabi.GdrnHipError(f"pose metrics run on the GPU (no CPU fallback): {what} is not a device tensor")
-    t = t.detach().to(torch.float64).reshape(shape).contiguous()   # fp32 -> fp64 widens exactly
-    return t
-
-
-def _labels(labels, N, device):
-    """(int32 device tensor, int32 host array): labels from the host (list / numpy / CPU tensor -- where a data loader has them) are uploaded;
-    a device tensor is copied back once, because the range check happens on the host before anything is launched."""
-    if isinstance(labels, torch.Tensor):
-        host = labels.detach().cpu().numpy()
-    else:
-        host = np.asarray(labels)
-    host = np.ascontiguousarray(host.reshape(-1).astype(np.int32))
-    if host.shape[0] != N:
-        raise ValueError(f"{host.shape[0]} labels for {N} rows")
-    if isinstance(labels, torch.Tensor) and labels.device.type == "cuda":
-        dev = labels.detach().reshape(-1).to(torch.int32).contiguous()
-    else:
-        dev = torch.from_numpy(host).to(device)
-    return dev, host
 
 
 def _errors(table, R_est, t_est, R_gt, t_gt, K, labels):
     N = int(R_est.shape[0]) if isinstance(R_est, torch.Tensor) else 0
-    R_est, R_gt, K = _f64(R_est, (-1, 3, 3), "R_est"), _f64(R_gt, (-1, 3, 3), "R_gt"), _f64(K, (-1, 3, 3), "K")
-    t_est, t_gt = _f64(t_est, (-1, 3), "t_est"), _f64(t_gt, (-1, 3), "t_gt")
+    R_est, R_gt, K = (devargs.device_tensor(m, torch.float64, (-1, 3, 3), what, WHERE) for m, what in ((R_est, "R_est"), (R_gt, "R_gt"), (K, "K")))
+    t_est, t_gt = (devargs.device_tensor(v, torch.float64, (-1, 3), what, WHERE) for v, what in ((t_est, "t_est"), (t_gt, "t_gt")))
     dev = R_est.device
-    if K.shape[0] == 1 and N > 1:
-        K = K.expand(N, 3, 3).contiguous()
-    if not (R_gt.shape[0] == K.shape[0] == t_est.shape[0] == t_gt.shape[0] == N):
-        raise ValueError("R_est, t_est, R_gt, t_gt and K need one entry per row")
+    K = devargs.per_row_K(K, N)
+    if not (R_gt.shape[0] == t_est.shape[0] == t_gt.shape[0] == N):
+        raise ValueError("R_est, t_est, R_gt and t_gt need one entry per row")
     lib = cabi.load()
-    lab, lab_host = _labels(labels, N, dev)
+    lab, lab_host = devargs.index_vector(labels, N, None, dev, "labels")   # (their range: the library refuses a label outside the table)
     tb = table.on(dev)
     err = torch.empty(max(N, 1), 4, dtype=torch.float64, device=dev)[:N]
-    ws_bytes = int(lib.gdrn_pose_metrics_workspace_bytes(N, table.n_max))
-    ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    ws = devargs.workspace(lib.gdrn_pose_metrics_workspace_bytes(N, table.n_max), dev, "pose_metrics_workspace_bytes")
+    st = devargs.stream(dev)
     cabi.check(lib.gdrn_pose_errors(cabi.ptr(R_est), cabi.ptr(t_est), cabi.ptr(R_gt), cabi.ptr(t_gt), cabi.ptr(K), cabi.ptr(lab),
                                     lab_host.ctypes.data, N, cabi.ptr(tb["pts"]), cabi.ptr(tb["npts"]), table.n_max, cabi.ptr(tb["is_sym"]),
                                     cabi.ptr(tb["sym"]), cabi.ptr(tb["nsym"]), table.k_max, table.num_classes, cabi.ptr(err), cabi.ptr(ws), st),
@@ -168,10 +131,10 @@ class PoseRecall:
         err, lab, lab_host = _errors(self.table, R_est, t_est, R_gt, t_gt, K, labels)
         dev = err.device
         v, tb = self._on(dev), self.table.on(dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
         cabi.check(cabi.load().gdrn_pose_recall_accumulate(cabi.ptr(err), cabi.ptr(lab), lab_host.ctypes.data, err.shape[0], cabi.ptr(tb["diameter"]),
                                                            self.table.num_classes, cabi.ptr(v["hits"]), cabi.ptr(v["seen"]), cabi.ptr(v["re_sum"]),
-                                                           cabi.ptr(v["te_sum"]), cabi.ptr(v["err_cnt"]), st), "pose_recall_accumulate")
+                                                           cabi.ptr(v["te_sum"]), cabi.ptr(v["err_cnt"]), devargs.stream(dev)),
+                   "pose_recall_accumulate")
 
     def add_missing(self, label, count=1, device=None):
         if not 0 <= int(label) < self.table.num_classes or int(count) < 0:

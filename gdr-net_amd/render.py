@@ -10,15 +10,18 @@ of ``near`` is dropped whole) are stated with the entry points in ``include/gdrn
 import numpy as np
 import torch
 
-from . import cabi
+from . import cabi, devargs
 
 NEAR, FAR = 0.01, 6.5   # the tool's values (lm_pbr_1_gen_xyz_crop.py:48-49)
+WHERE = "the renderer"   # (this module in devargs' error sentence)
 
 
-class MeshTable:
+class MeshTable(devargs.DeviceTables):
     """Per-class triangle meshes, packed once without padding: ``vertices_list`` a list of [n_c,3] arrays in metres (kept as fp64), ``faces_list`` a
     list of [f_c,3] integer arrays of vertex indices within the class (kept as int32, range-checked here).  ``verts`` / ``faces`` are the
     concatenations, class c owning the rows ``vert_off[c] : vert_off[c] + nverts[c]`` and ``face_off[c] : face_off[c] + nfaces[c]``."""
+
+    TABLES = ("verts", "faces", "vert_off", "nverts", "face_off", "nfaces")
 
     def __init__(self, vertices_list, faces_list, device=None):
         C = len(vertices_list)
@@ -46,67 +49,24 @@ class MeshTable:
         self.f_max = int(self.nfaces.max())
         self.verts = np.ascontiguousarray(np.concatenate(vs, axis=0))
         self.faces = np.ascontiguousarray(np.concatenate(fs, axis=0))
-        self._dev = {}
         if device is not None:
             self.on(device)
-
-    def check_labels(self, labels):
-        """labels (list / numpy / tensor) as a contiguous int32 host array, each within [0, num_classes): raises ValueError otherwise."""
-        host = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
-        host = np.ascontiguousarray(host.reshape(-1).astype(np.int32))
-        if host.size and (host.min() < 0 or host.max() >= self.num_classes):
-            raise ValueError(f"label outside [0, {self.num_classes})")
-        return host
-
-    def on(self, device):
-        """the tables as device tensors (uploaded once per device)."""
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = {k: torch.from_numpy(getattr(self, k)).to(device) for k in ("verts", "faces", "vert_off", "nverts", "face_off", "nfaces")}
-        return self._dev[key]
-
-
-def _dev(t, dtype, shape, what):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise cabi.GdrnHipError(f"{what} must be a device tensor: the renderer runs on the GPU (no CPU fallback)")
-    return t.detach().to(dtype).reshape(shape).contiguous()   # fp32 -> fp64 widens exactly
-
-
-def _poses(R, t, K):
-    R, t, K = _dev(R, torch.float64, (-1, 3, 3), "R"), _dev(t, torch.float64, (-1, 3), "t"), _dev(K, torch.float64, (-1, 3, 3), "K")
-    N = int(R.shape[0])
-    if K.shape[0] == 1 and N > 1:
-        K = K.expand(N, 3, 3).contiguous()
-    if not (t.shape[0] == K.shape[0] == N):
-        raise ValueError("R, t and K need one entry per instance")
-    return R, t, K, N
-
-
-def _labels(table, labels, N, device):
-    """(int32 device tensor, int32 host array), range-checked on the host before anything is launched; a device tensor is copied back once for it."""
-    host = table.check_labels(labels)
-    if host.shape[0] != N:
-        raise ValueError(f"{host.shape[0]} labels for {N} instances")
-    if isinstance(labels, torch.Tensor) and labels.device.type == "cuda":
-        return labels.detach().reshape(-1).to(torch.int32).contiguous(), host
-    return torch.from_numpy(host).to(device), host
 
 
 def render_depth(table, labels, R, t, K, H, W, near=NEAR, far=FAR):
     """Depth [N,H,W] fp32 (camera-space z in metres, 0 where nothing is drawn) of N instances in one call: instance i is the mesh ``labels[i]`` of
     ``table`` under the pose ``R[i]``, ``t[i]`` (model to camera, metres) seen through ``K[i]`` (upper triangular; [3,3] is shared by all).
     R, t, K: device tensors, fp32 or fp64.  A triangle with a vertex at z < near is dropped whole (no near-plane clipping)."""
-    R, t, K, N = _poses(R, t, K)
+    R, t, K, N = devargs.poses(R, t, K, WHERE)
     dev = R.device
-    lab, lab_host = _labels(table, labels, N, dev)
+    lab, lab_host = devargs.index_vector(labels, N, table.num_classes, dev, "labels")
     tb = table.on(dev)
     H, W = int(H), int(W)
     depth = torch.empty(max(N, 0), max(H, 0), max(W, 0), dtype=torch.float32, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
     p = cabi.ptr
     cabi.check(cabi.load().gdrn_render_depth(p(tb["verts"]), p(tb["faces"]), p(tb["vert_off"]), p(tb["nverts"]), p(tb["face_off"]), p(tb["nfaces"]),
                                              table.num_classes, table.f_max, p(lab), lab_host.ctypes.data, p(R), p(t), p(K), N, H, W, float(near),
-                                             float(far), p(depth), st), "render_depth")
+                                             float(far), p(depth), devargs.stream(dev)), "render_depth")
     return depth
 
 
@@ -114,20 +74,19 @@ def xyz_from_depth(depth, R, t, K):
     """``calc_xyz_bp_fast`` + ``mask2bbox_xyxy`` for a batch of depth maps [N,H,W] (from ``render_depth`` or the caller's own): a dict of device
     tensors ``xyz`` [N,H,W,3] fp32 = R^T (depth K^-1 [x,y,1] - t) evaluated in fp64, 0 where depth is 0; ``mask`` [N,H,W] u8; ``xyxy`` [N,4] int32,
     the inclusive bounds of the mask; ``visible`` [N] int32.  An empty mask gives xyxy = [0, 0, W-1, H-1] and visible = 0, as the tool writes it."""
-    depth = _dev(depth, torch.float32, tuple(depth.shape) if isinstance(depth, torch.Tensor) else (-1,), "depth")
+    depth = devargs.device_tensor(depth, torch.float32, None, "depth", WHERE)
     if depth.dim() != 3:
         raise ValueError("depth must be [N, H, W]")
-    R, t, K, N = _poses(R, t, K)
+    R, t, K, N = devargs.poses(R, t, K, WHERE)
     if depth.shape[0] != N:
         raise ValueError("depth, R, t and K need one entry per instance")
     dev = depth.device
     H, W = int(depth.shape[1]), int(depth.shape[2])
     out = dict(xyz=torch.empty(N, H, W, 3, dtype=torch.float32, device=dev), mask=torch.empty(N, H, W, dtype=torch.uint8, device=dev),
                xyxy=torch.empty(N, 4, dtype=torch.int32, device=dev), visible=torch.empty(N, dtype=torch.int32, device=dev))
-    st = torch.cuda.current_stream(dev).cuda_stream
     p = cabi.ptr
     cabi.check(cabi.load().gdrn_xyz_from_depth(p(depth), p(R), p(t), p(K), N, H, W, p(out["xyz"]), p(out["mask"]), p(out["xyxy"]), p(out["visible"]),
-                                               st), "xyz_from_depth")
+                                               devargs.stream(dev)), "xyz_from_depth")
     return out
 
 

@@ -18,23 +18,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _timing import timed, write_json  # noqa: E402
 from gdrnet_amd import augment as A, synth  # noqa: E402
 from gdrnet_amd.cfg import lmo_cfg  # noqa: E402
 
 B, H, W, BANK, SEED = 64, 480, 640, 8, 17
-
-
-def timed(fn, warmup=5, calls=20):
-    times = []
-    for it in range(warmup + calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        if it >= warmup:
-            times.append(e0.elapsed_time(e1))
-    return times
 
 
 def plans(aug):
@@ -69,15 +57,13 @@ def main():
         prep = aug.prepare(frames, masks if with_mask else None, plan)
         nbytes = B * H * W * (3 + 3 + (2 if with_mask else 0))
         for call, fn in (("apply", lambda: aug.apply(frames, masks if with_mask else None, plan)), ("launch", lambda: aug.launch(prep))):
-            times = timed(fn)
+            times = timed(fn)[1]
             ms = statistics.median(times)
             row = dict(call=f"{call}, {name}", frames=B, H=H, W=W, gpu_ms_median=ms, gpu_ms_min=min(times), gpu_ms_max=max(times),
                        frames_per_s=B / ms * 1e3, gb_per_s=nbytes / ms / 1e6)
             res.append(row)
             print(json.dumps(row), flush=True)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as fh:
-            json.dump(dict(device=torch.cuda.get_device_name(0), results=res), fh, indent=1)
+    write_json(res)
 
 
 if __name__ == "__main__":

@@ -18,22 +18,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bop_host as BH  # noqa: E402
+from _timing import timed, write_json  # noqa: E402
 from gdrnet_amd import bop_metrics as BM, render, synth  # noqa: E402
 
 HOST_ROWS = 8
-
-
-def timed(fn, warmup=5, calls=20):
-    times, out = [], None
-    for it in range(warmup + calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn()
-        e1.record()
-        e1.synchronize()
-        if it >= warmup:
-            times.append(e0.elapsed_time(e1))
-    return out, times
 
 
 def report(res, call, times, **extra):
@@ -113,9 +101,7 @@ def main():
         row["host_rows_timed"] = HOST_ROWS
         row["worst_abs_diff_to_host"] = [float(np.abs(ref[:, k] - e[:HOST_ROWS, k]).max()) for k in (0, 1)]
         show(row)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as fh:
-            json.dump(dict(device=torch.cuda.get_device_name(0), results=res), fh, indent=1)
+    write_json(res)
 
 
 if __name__ == "__main__":

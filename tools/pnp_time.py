@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import pnp_host as H  # noqa: E402
+from _timing import timed, write_json  # noqa: E402
 from gdrnet_amd import pnp, synth  # noqa: E402
 
 
@@ -39,15 +40,7 @@ def main():
     assert torch.cuda.is_available(), "needs an MI355X"
     dev, a = "cuda:0", inputs()
     img, mod, cnt, K = (torch.from_numpy(a[k]).to(dev) for k in ("img", "mod", "counts", "K"))
-    times = []
-    for it in range(25):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = pnp.pnp_ransac(img, mod, cnt, K, reproj_err=3.0, iters=100, seed=0, want_mask=True)
-        e1.record()
-        e1.synchronize()
-        if it >= 5:
-            times.append(e0.elapsed_time(e1))
+    out, times = timed(lambda: pnp.pnp_ransac(img, mod, cnt, K, reproj_err=3.0, iters=100, seed=0, want_mask=True))
     ok, mask = out["ok"].cpu().numpy(), out["inlier_mask"].cpu().numpy().astype(bool)
     Rg, tg = out["R"].cpu().numpy(), out["t"].cpu().numpy()
     t0 = time.perf_counter()
@@ -62,9 +55,7 @@ def main():
                gpu_ms_max=max(times), host_ms_refine_only=host_ms, solved=int(ok.sum()), masks_equal_truth=bool((mask == a["good"]).all()),
                worst_deviation_from_host=worst)
     print(json.dumps(row), flush=True)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(dict(device=torch.cuda.get_device_name(0), results=[row]), f, indent=1)
+    write_json([row])
 
 
 if __name__ == "__main__":

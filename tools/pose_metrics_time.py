@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import timed, write_json  # noqa: E402
 from gdrnet_amd import pose_metrics as PM, synth  # noqa: E402
 
 
@@ -39,15 +40,7 @@ def main():
     for name, n, sym in (("n=16384 symmetric (adi)", 16384, True), ("n=16384 non-symmetric (add)", 16384, False), ("n=3000 symmetric (adi)", 3000, True)):
         table, pts, host, labels = inputs(N, n, sym)
         poses = [torch.from_numpy(host[k]).to(dev) for k in ("R_est", "t_est", "R_gt", "t_gt", "K")]
-        times = []
-        for it in range(25):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = PM.pose_errors(table, *poses, labels)
-            e1.record()
-            e1.synchronize()
-            if it >= 5:
-                times.append(e0.elapsed_time(e1))
+        out, times = timed(lambda: PM.pose_errors(table, *poses, labels))
         row = dict(shape=name, N=N, gpu_ms_median=statistics.median(times), gpu_ms_min=min(times), gpu_ms_max=max(times))
         try:
             from scipy import spatial
@@ -67,9 +60,7 @@ def main():
             pass
         res.append(row)
         print(json.dumps(row), flush=True)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(dict(device=torch.cuda.get_device_name(0), results=res), f, indent=1)
+    write_json(res)
 
 
 if __name__ == "__main__":

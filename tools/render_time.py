@@ -11,20 +11,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import timed, write_json  # noqa: E402
 from gdrnet_amd import render, synth  # noqa: E402
-
-
-def timed(fn, warmup=5, calls=20):
-    times, out = [], None
-    for it in range(warmup + calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn()
-        e1.record()
-        e1.synchronize()
-        if it >= warmup:
-            times.append(e0.elapsed_time(e1))
-    return out, times
 
 
 def main():
@@ -46,9 +34,7 @@ def main():
                    mpixel_per_s=N * H * W / ms / 1e3)
         res.append(row)
         print(json.dumps(row), flush=True)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as fh:
-            json.dump(dict(device=torch.cuda.get_device_name(0), results=res), fh, indent=1)
+    write_json(res)
 
 
 if __name__ == "__main__":

@@ -18,22 +18,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _timing import timed, write_json  # noqa: E402
 from gdrnet_amd import cabi, masks as M  # noqa: E402
 
 B, H, W, SEED = 64, 480, 640, 23
-
-
-def timed(fn, warmup=5, calls=20):
-    times = []
-    for it in range(warmup + calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        if it >= warmup:
-            times.append(e0.elapsed_time(e1))
-    return times
 
 
 def silhouettes():
@@ -61,7 +49,7 @@ def main():
     res = []
 
     def report(call, fn, gb=None):
-        times = timed(fn)
+        times = timed(fn)[1]
         ms = statistics.median(times)
         row = dict(call=call, masks=B, H=H, W=W, gpu_ms_median=ms, gpu_ms_min=min(times), gpu_ms_max=max(times), masks_per_s=B / ms * 1e3)
         if gb:
@@ -113,9 +101,7 @@ def main():
     report("encode + to_coco, both reads", lambda: M.encode(masks).to_coco())
     report("stats (area, bbox) alone", lambda: M.stats(masks), nbytes)
     print(json.dumps(dict(string_bytes=int(batch.offsets[-1]), mask_bytes=nbytes)), flush=True)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as fh:
-            json.dump(dict(device=torch.cuda.get_device_name(0), string_bytes=int(batch.offsets[-1]), results=res), fh, indent=1)
+    write_json(res, string_bytes=int(batch.offsets[-1]))
 
 
 if __name__ == "__main__":
