@@ -273,11 +273,15 @@ _SIGS = {
     "gdrn_rle_count": [P, C.POINTER(RleTask), I, P, LL, P, P, P],
     "gdrn_rle_positions": [P, C.POINTER(RleTask), I, P, LL, P, P, LL, P],
     "gdrn_rle_string": [P, C.POINTER(RleTask), I, P, P, LL, P, P, LL, P, P],
+    "gdrn_model_prep_workspace_bytes": [I, I, I],
+    "gdrn_model_bounds": [P, P, P, I, I, P, P],
+    "gdrn_model_fps": [P, P, P, I, I, I, P, P, P, P],
+    "gdrn_model_diameter": [P, P, P, I, I, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []
 _RET_LL = ("gdrn_workspace_bytes", "gdrn_pose_metrics_workspace_bytes", "gdrn_pnp_workspace_bytes", "gdrn_vsd_workspace_bytes",
-           "gdrn_mssd_mspd_workspace_bytes")
+           "gdrn_mssd_mspd_workspace_bytes", "gdrn_model_prep_workspace_bytes")
 EXPORTS = tuple(_SIGS.keys())
 _libs = {}
 

@@ -733,3 +733,46 @@ def bop_test_depth(inp, depth_gt):
     cx, cy = (x1 + x2) // 2, (y1 + y2) // 2
     out[int(inp["frame"][inp["holes_row"]]), cy : cy + 4, cx : cx + 5] = 0.0
     return out.astype(np.float32)
+
+
+# ----------------------------------------------------------------------------------------------
+# vertex clouds of the model preparation (gdrnet_amd.model_prep, golden G16)
+# ----------------------------------------------------------------------------------------------
+MODEL_PREP_SEED = 161
+MODEL_PREP_CASES = ("rand1000", "rand1029", "rand8209", "rand70000", "sphere642", "grid125", "repeat20", "single")
+MODEL_PREP_BOX = np.array([0.12, 0.08, 0.2])   # metres: the size of an LM object
+
+
+def make_model_prep_inputs(case):
+    """[n,3] fp64 vertices of one object of golden G16 (the reference's FPS, diameter and box on them); deterministic, nothing is read.
+
+    "rand<n>"    n points uniform in a 0.12 x 0.08 x 0.2 m box (fp64 values that fp32 does not hold: the rounding is part of the case)
+    "sphere642"  the perturbed icosphere (subdivision 3) of 0.05 m radius
+    "grid125"    the 5 x 5 x 5 grid of spacing 0.25: exact ties throughout, and its centre point sits exactly on the centre of the box
+    "repeat20"   5 distinct points, 4 times over: any K above 5 is beyond the number of distinct points
+    "single"     one point"""
+    u = lambda tag, *shape: hash_uniform(MODEL_PREP_SEED, f"{case}/{tag}", shape)  # noqa: E731
+    if case.startswith("rand"):
+        return (u("p", int(case[4:]), 3) - 0.5) * MODEL_PREP_BOX
+    if case == "sphere642":
+        return mesh_icosphere(3, 0.05, 0.35, MODEL_PREP_SEED)[0]
+    if case == "grid125":
+        g = np.arange(5, dtype=np.float64) * 0.25 - 0.5
+        return np.stack(np.meshgrid(g, g, g, indexing="ij"), axis=-1).reshape(-1, 3)
+    if case == "repeat20":
+        return np.tile((u("p", 5, 3) - 0.5) * MODEL_PREP_BOX, (4, 1))
+    if case == "single":
+        return (u("p", 1, 3) - 0.5) * MODEL_PREP_BOX
+    raise ValueError(case)
+
+
+def model_prep_shells(subdivisions, seed=MODEL_PREP_SEED):
+    """one cloud from concentric perturbed icospheres (``mesh_icosphere`` with perturb 0.35), shell j of radius 0.05 (1 - 0.1 j) m and its own seed:
+    a scanned object's vertex count without a file -- 10 * 4^s + 2 vertices per shell of subdivision s"""
+    return np.concatenate([mesh_icosphere(s, 0.05 * (1.0 - 0.1 * j), 0.35, seed + j)[0] for j, s in enumerate(subdivisions)], axis=0)
+
+
+def make_model_prep_workload():
+    """the clouds tools/model_prep_time.py times: 21 objects of 16 008 vertices (shells of subdivision 5, 4, 4, 3) and one of 259 854 (7, 6, 6, 5,
+    4, 3, 3), the sizes of a dataset of CAD models with one scanned mesh among them"""
+    return [model_prep_shells((5, 4, 4, 3), MODEL_PREP_SEED + 10 * c) for c in range(21)] + [model_prep_shells((7, 6, 6, 5, 4, 3, 3), MODEL_PREP_SEED + 500)]

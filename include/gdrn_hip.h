@@ -948,6 +948,30 @@ int gdrn_rle_string(const gdrn_rle_task* tasks_dev, const gdrn_rle_task* tasks_h
                     long long pos_cap, const long long* str_offsets, unsigned char* strings, long long strings_bytes, long long* lengths,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Model preparation on the device (added within ABI 5: new entry points, nothing changed): the per-object tables the data-side and evaluation-side
+ * modules take -- extents and 3D box (core/gdrn_modeling/data_loader.py:243-276, misc.get_bbox3d_and_center, lib/pysixd/misc.py:982-1030),
+ * farthest-point-sampling (FPS) points (sample_farthest_points_init_center, core/csrc/fps/src/farthest_point_sampling.cpp:122-160, what
+ * fps_points.pkl holds) and diameters (misc.calc_pts_diameter, misc.py:952-966) -- for all C objects per call.
+ *   pts [C][n_max][3] fp64 with npts [C] int32 valid rows each (device; the rows behind are never read), npts_host the same C values in host
+ *   memory: the arguments are checked on them before anything is launched.
+ * gdrn_model_bounds: bounds [C][9] fp64 = per-axis minimum, maximum (both exact) and mean (sum in a fixed order, divided by the count).
+ * gdrn_model_fps: idx [C][K] int32 = the reference's index sequence with init_center, bit for bit: the vertices rounded to fp32 (nearest even),
+ *   the first index the point farthest from (max + min) * 0.5f of the fp32 box, then K - 1 times the point whose minimum squared distance
+ *   (dx dx + dy dy) + dz dz (fp32, every operation rounded) to the indices so far is largest; among equal maxima the lowest index, and index 0
+ *   when no distance is above 0 (K beyond the number of distinct points).  The sequence for K is a prefix of the one for any larger K.
+ *   xyz [C][K][3] fp64 (may be NULL) = the fp32-rounded vertices at idx.  One workgroup per object, one launch.  workspace:
+ *   gdrn_model_prep_workspace_bytes(C, n_max, K) bytes of 16-byte aligned device memory, no initialisation needed (0 bytes: may be NULL).
+ * gdrn_model_diameter: max_sq [C] fp64 = the maximum over all pairs of an object's points of (dx dx + dy dy) + dz dz in fp64, every operation
+ *   rounded; the diameter is its sqrt.  A maximum: the same bits for any pair order.
+ * Status: GDRN_ERR_ARG for a NULL pointer, C < 1, n_max < 1, a point count outside [1, n_max], K < 1 or a missing / misaligned workspace;
+ *   GDRN_ERR_SHAPE for n_max * 3 >= 2^31, C > 65535 or (diameter) 2^32 threads and more in the launch.  No call allocates or reads anything back. */
+long long gdrn_model_prep_workspace_bytes(int C, int n_max, int K);
+int gdrn_model_bounds(const double* pts, const int* npts, const int* npts_host, int C, int n_max, double* bounds, void* stream);
+int gdrn_model_fps(const double* pts, const int* npts, const int* npts_host, int C, int n_max, int K, int* idx, double* xyz, void* workspace,
+                   void* stream);
+int gdrn_model_diameter(const double* pts, const int* npts, const int* npts_host, int C, int n_max, double* max_sq, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
