@@ -687,16 +687,21 @@ __global__ __launch_bounds__(256) void gn_relu_fwd_kernel(const T* __restrict__ 
     constexpr int V = Vec16<T>::VEC;
     __shared__ double sg[2 * 128];
     __shared__ float kgb[2][512];
-    __shared__ float pp[2][256 * V];  // per-thread partial sums [row lane][channel]: added up in a fixed order (no atomics -> reproducible)
+    // per-thread partial sums [row lane][channel]: added up in a fixed order (no atomics -> reproducible).  fp32 storage (the parity mode): fp64
+    // from the first addition on -- a group mean close to 0 is the difference of sums hundreds of times its size, and fp32 partial sums cost it
+    // several ulp.  16-bit storage: fp32 per thread, fp64 from the tree on -- operands of 8 / 11 significant bits mostly add up exactly over a
+    // thread's few rows, but nothing guarantees the mean to an ulp there (it sits far below the storage format's own 2^-9 / 2^-12 either way).
+    typedef typename std::conditional<std::is_same<T, float>::value, double, float>::type acc_t;
+    __shared__ acc_t pp[2][256 * V];
     const int n = blockIdx.x, cpg = C / G, c0 = blockIdx.y * CS, g0 = c0 / cpg, GS = CS / cpg;
     const int tpr = CS / V, rpp = 256 / tpr;
     const int cv = threadIdx.x % tpr, rl = threadIdx.x / tpr;
     for (int i = threadIdx.x; i < CS; i += 256) { kgb[0][i] = gamma[c0 + i]; kgb[1][i] = beta[c0 + i]; }
     __syncthreads();
     const T* xb = x + (size_t)n * HW * C + c0;
-    float s1[V], s2[V];
+    acc_t s1[V], s2[V];
 #pragma unroll
-    for (int j = 0; j < V; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+    for (int j = 0; j < V; ++j) { s1[j] = 0; s2[j] = 0; }
     // (r6b) a thread's rows -- up to GN_NC of them: the 32 x 32 and smaller maps of the path at 32-channel slabs -- stay in registers between the
     // statistics pass and the normalisation: the slab is read once, and the second pass starts without a memory round trip
     constexpr int GN_NC = 16;
@@ -715,7 +720,7 @@ __global__ __launch_bounds__(256) void gn_relu_fwd_kernel(const T* __restrict__ 
                 float v[V];
                 Vec16<T>::unpack(xc[u], v);
 #pragma unroll
-                for (int j = 0; j < V; ++j) { s1[j] += v[j]; s2[j] += v[j] * v[j]; }
+                for (int j = 0; j < V; ++j) { s1[j] += (acc_t)v[j]; s2[j] += (acc_t)v[j] * (acc_t)v[j]; }
             }
         }
     } else {
@@ -723,7 +728,7 @@ __global__ __launch_bounds__(256) void gn_relu_fwd_kernel(const T* __restrict__ 
             float v[V];
             Vec16<T>::load(xb + (size_t)r * C + cv * V, v);
 #pragma unroll
-            for (int j = 0; j < V; ++j) { s1[j] += v[j]; s2[j] += v[j] * v[j]; }
+            for (int j = 0; j < V; ++j) { s1[j] += (acc_t)v[j]; s2[j] += (acc_t)v[j] * (acc_t)v[j]; }
         }
     }
     if (rl < rpp) {
@@ -1037,7 +1042,8 @@ extern "C" int gdrn_bn_eval_params(const float* gamma, const float* beta, const 
 
 extern "C" int gdrn_bn_apply(const void* x, const float* scale, const float* shift, const void* residual, void* y,
                              long long npix, int C, int relu, int dtype, void* stream) {
-    if (!x || !scale || !shift || !y || npix <= 0 || C <= 0 || (C % 8)) return GDRN_ERR_ARG;
+    // (C <= 512: bn_apply_kernel stages scale / shift in kst[2][512])
+    if (!x || !scale || !shift || !y || npix <= 0 || C <= 0 || C > 512 || (C % 8)) return GDRN_ERR_ARG;
     const int V = dtype == GDRN_DT_H16 ? 8 : 4;
     if ((C / V) > 256 || 256 % (C / V)) return GDRN_ERR_SHAPE;
     int rpb, blocks;

@@ -304,6 +304,8 @@ int gdrn_bn_finalize(const float* partial, int rows, int C, double count, const 
                      float eps, float* mean, float* invstd, float* scale, float* shift, double* ws, void* stream);
 int gdrn_bn_eval_params(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                         float eps, int C, float* scale, float* shift, void* stream);
+/* y = x*scale + shift (+ residual) (then ReLU), NHWC [npix][C].  C % 8 == 0 and C <= 512 (GDRN_ERR_ARG otherwise: the kernel stages the
+ * per-channel constants in a 512-entry LDS array, like gdrn_bn_bwd_reduce / gdrn_bn_bwd_apply); C / V (V = 4 fp32, 8 16-bit) divides 256. */
 int gdrn_bn_apply(const void* x, const float* scale, const float* shift, const void* residual, void* y,
                   long long npix, int C, int relu, int dtype, void* stream);
 /* BatchNorm backward = (1) per-channel sums of g and g*xhat, g = dy * (ymask > 0) * (x*mask_scale + mask_shift > 0) (each mask

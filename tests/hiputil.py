@@ -176,3 +176,80 @@ def conv_wgrad(x, dy, B, Hi, Wi, Cin, x_cs, Ho, Wo, Cout, dy_cs, KH, KW, stride,
 def randn(seed, *shape):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(*shape, generator=g)
+
+
+# ---------------------------------------------------------------------------------------------- helpers of tests/test_norm_edges_gpu.py
+KIND = {F32: "fp32", BF16: "bf16", F16: "fp16"}   # the storage-type names of tests/norm_host.py
+
+
+def to_dev(a, dt):
+    """numpy array of values that are exact in storage type dt -> device tensor of that type"""
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).to(tdt(dt)).to(DEV).contiguous()   # (converted on the host)
+
+
+def f32_dev(a):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).to(DEV)
+
+
+def nans(shape, dtype=torch.float32):
+    """an output buffer no element of which may survive (uint8: 0xff, not a tap code)"""
+    if dtype == torch.uint8:
+        return torch.full(tuple(shape), 255, dtype=dtype, device=DEV)
+    return torch.full(tuple(shape), float("nan"), dtype=dtype, device=DEV)
+
+
+def to_host(t):
+    return t.detach().cpu().to(torch.float64).numpy()
+
+
+def rows_buf(nrows, C_):
+    """partial-row buffer sized by the library's own *_rows query plus ONE guard row of NaN that must stay NaN"""
+    return nans((nrows + 1, 2, C_))
+
+
+def rows_total(buf, nrows):
+    """fp64 sum of the partial rows; every row written (no NaN left), the guard row untouched"""
+    torch.cuda.synchronize()
+    h = to_host(buf)
+    assert not np.isnan(h[:nrows]).any(), "a partial row was not written"
+    assert np.isnan(h[nrows]).all(), "the guard row behind the partial rows was written"
+    return h[:nrows].sum(0)
+
+
+def assert_within(got, ref, bnd, what, exact=None):
+    """per element |got - ref| <= bnd (no NaN); where `exact` is set got == ref bit for bit.  Reports the first few offenders with their index."""
+    got, ref, bnd = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64), np.broadcast_to(np.asarray(bnd, dtype=np.float64), np.shape(ref))
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    bad = ~(np.abs(got - ref) <= bnd)     # (NaN compares false: an unwritten element is an offender)
+    if exact is not None:
+        bad |= np.broadcast_to(exact, ref.shape) & (got != ref)
+    if bad.any():
+        idx = np.argwhere(bad)
+        lines = [f"  {tuple(int(v) for v in i)}: got {got[tuple(i)]!r} want {ref[tuple(i)]!r} bound {bnd[tuple(i)]:.3e}" for i in idx[:6]]
+        raise AssertionError(f"{what}: {len(idx)} of {bad.size} elements outside their bound, first at\n" + "\n".join(lines))
+
+
+def assert_same(got, want, what):
+    """exact comparison of discrete outputs (tap codes, masks, bit patterns) with an index report"""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = got != want
+    if bad.any():
+        idx = np.argwhere(bad)
+        lines = [f"  {tuple(int(v) for v in i)}: got {got[tuple(i)]!r} want {want[tuple(i)]!r}" for i in idx[:6]]
+        raise AssertionError(f"{what}: {len(idx)} of {bad.size} elements differ, first at\n" + "\n".join(lines))
+
+
+class Guarded:
+    """an output tensor of `shape` pre-filled with NaN (uint8: 0xff) inside a buffer with one more innermost row behind it that must stay as it is"""
+
+    def __init__(self, shape, dtype):
+        self.n = int(np.prod(shape))
+        self.buf = nans((self.n + int(shape[-1]),), dtype)
+        self.t = self.buf[:self.n].view(tuple(shape))
+
+    def host(self, what="output"):
+        torch.cuda.synchronize()
+        tail = self.buf[self.n:]
+        assert bool((tail == 255).all() if tail.dtype == torch.uint8 else torch.isnan(tail).all()), f"{what}: written past its end"
+        return self.t.cpu().numpy() if self.t.dtype == torch.uint8 else to_host(self.t)
