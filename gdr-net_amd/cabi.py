@@ -277,6 +277,9 @@ _SIGS = {
     "gdrn_model_bounds": [P, P, P, I, I, P, P],
     "gdrn_model_fps": [P, P, P, I, I, I, P, P, P, P],
     "gdrn_model_diameter": [P, P, P, I, I, P, P],
+    "gdrn_scene_gt_canvas": [P, I, I, I, I, I, P, P, P, P],
+    "gdrn_scene_gt_compose": [P, P, P, P, P, I, I, I, I, P, P],
+    "gdrn_scene_gt_visibility": [P, P, P, P, I, P, I, I, I, D, I, P, P, P, P, P, P, P, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []

@@ -14,6 +14,7 @@
 // operation is an explicit fma().  (No 16-bit code: both library builds compile the same thing.)
 #include "common.h"
 #include "geom64.h"
+#include "dist64.h"
 #include "../../include/gdrn_hip.h"
 
 #pragma clang fp contract(off)
@@ -62,11 +63,7 @@ __global__ __launch_bounds__(BM_THREADS) void vsd_clear_kernel(long long* __rest
     if (i < n) counts[i] = 0;
 }
 
-// misc.depth_im_to_dist_im_fast: sqrt((X d)^2 + (Y d)^2 + d^2), X = (x - cx) / fx, Y = (y - cy) / fy
-__device__ __forceinline__ double dist_of(double X, double Y, float depth) {
-    const double d = (double)depth, a = X * d, b = Y * d;
-    return sqrt((a * a + b * b) + d * d);
-}
+// (misc.depth_im_to_dist_im_fast per pixel: dist_of, dist64.h)
 
 // Workgroup (chunk of VSD_CHUNK pixels, row).  Per pixel the two visibility masks; union, union - intersection and the per-tau step costs are
 // counted per wave by ballot / popcount, gathered in LDS and added to the row's counters with one integer atomic per workgroup and counter.

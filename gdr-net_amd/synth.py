@@ -776,3 +776,65 @@ def make_model_prep_workload():
     """the clouds tools/model_prep_time.py times: 21 objects of 16 008 vertices (shells of subdivision 5, 4, 4, 3) and one of 259 854 (7, 6, 6, 5,
     4, 3, 3), the sizes of a dataset of CAD models with one scanned mesh among them"""
     return [model_prep_shells((5, 4, 4, 3), MODEL_PREP_SEED + 10 * c) for c in range(21)] + [model_prep_shells((7, 6, 6, 5, 4, 3, 3), MODEL_PREP_SEED + 500)]
+
+
+# ----------------------------------------------------------------------------------------------
+# scenes of the scene ground truth (gdrnet_amd.scene_gt, golden G17)
+# ----------------------------------------------------------------------------------------------
+SCENE_GT_SEED = 171
+# ^ the seed golden G17 was drawn with (tests/golden/make_golden_g17.py moves on while a pixel centre sits within 1e-6 px of an edge or a visibility
+#   difference within 1e-5 m of delta)
+SCENE_GT_CASES = ("mixed", "pad0")
+# (instance, what it is there for): tests/test_scene_gt_cpu.py asserts each on the host results
+SCENE_GT_KINDS = {"inside": 0, "truncated": 1, "outside_image": 2, "outside_canvas": 3, "partly_hidden": 4, "hider": 5, "fully_hidden": 6,
+                  "cover": 7, "pair": (8, 9), "occluded_left": 10, "single": 11}
+
+
+def make_scene_gt_inputs(case, seed=None):
+    """Scenes of golden G17, fp64, metres: dict(vertices, faces (one entry per class), labels, frame, num_frames, R, t, K (of the image, per
+    instance), H, W, pad, near, far, delta, background, occluded, holes_row, noise, seed).
+
+    "mixed"  12 instances in 3 frames of 47 x 61 (a ragged last chunk and wave) with pad = (61, 47): a canvas of 141 x 183.  Classes -- 0: a 0.1 m
+             cube, 1: the perturbed icosphere (subdivision 3), 2: a 0.12 x 0.09 m rectangle of 8 x 8 cells.  Frame 0 (instances 0-5): 0 fully
+             inside the image and unoccluded | 1 truncated by the right and bottom border | 2 wholly left of the image, inside the canvas |
+             3 outside the canvas | 4 a rectangle partly hidden by 5, a sphere 0.15 m in front of it.  Frame 1 (6-10): 6 a sphere fully hidden
+             behind the cube 7 | 8 and 9 two parallel rectangles 8 mm apart along the viewing direction (closer than delta: both visible) |
+             10 a cube whose left half ``scene_gt_depth`` puts behind an occluder.  Frame 2 (another camera): 11 alone.
+    "pad0"   the same scene with pad = (0, 0): in-image statistics only."""
+    if case not in SCENE_GT_CASES:
+        raise ValueError(case)
+    seed = SCENE_GT_SEED if seed is None else seed
+    u = lambda tag, *shape: hash_uniform(seed, tag, shape)  # noqa: E731
+    H, W, N = 47, 61, 12
+    rv, rf = mesh_rectangle(8, 8)
+    meshes = [mesh_cube(0.1), mesh_icosphere(3, 0.05, 0.35, seed), (rv * np.array([0.12, 0.09, 1.0]), rf)]
+    labels = np.array([1, 0, 1, 0, 2, 1, 1, 0, 2, 2, 0, 1], dtype=np.int64)
+    frame = np.array([0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 2], dtype=np.int64)
+    K1 = np.array([[70.0, 0.0, 30.3], [0.0, 71.0, 23.4], [0.0, 0.0, 1.0]])
+    K2 = np.array([[64.5, 0.0, 29.1], [0.0, 63.0, 22.2], [0.0, 0.0, 1.0]])
+    K = np.stack([K2 if f == 2 else K1 for f in frame])
+    R = _random_rotations(seed, "R", N)
+    for i in range(N):
+        if labels[i] == 2:   # the rectangles: roughly facing the camera
+            ax = hash_normal(seed, f"tilt{i}", (1, 3))
+            R[i] = _axis_angle(ax / np.linalg.norm(ax), np.array([25.0]))[0]
+    R[9] = R[8]
+    #                  0           1           2            3             4           5           6           7           8           9          10          11
+    centre = np.array([[14., 13.], [58., 38.], [-25., 20.], [400., 20.], [35., 14.], [41., 14.], [15., 15.], [15., 15.], [42., 13.], [43., 13.], [42., 35.], [30., 22.]])
+    z = np.array([0.50, 0.45, 0.50, 0.50, 0.55, 0.40, 0.70, 0.40, 0.500, 0.508, 0.50, 0.45])
+    jit = u("t_px", N, 2) - 0.5
+    jit[9] = jit[8]
+    jit[7] = jit[6]
+    centre = centre + jit
+    z = z + 0.01 * np.repeat(u("t_z", N // 2), 2)   # (pairs share their offset: 4 / 5, 6 / 7 and 8 / 9 keep their distance)
+    t = np.stack([(centre[:, 0] - K[:, 0, 2]) / K[:, 0, 0] * z, (centre[:, 1] - K[:, 1, 2]) / K[:, 1, 1] * z, z], axis=1)
+    return dict(vertices=[m[0] for m in meshes], faces=[m[1] for m in meshes], labels=labels, frame=frame, num_frames=3, R=R, t=t, K=K, H=H, W=W,
+                pad=(W, H) if case == "mixed" else (0, 0), near=0.01, far=6.5, delta=0.015, background=1.5, occluded={10: "left"}, holes_row=8,
+                noise=0.002, seed=seed)
+
+
+def scene_gt_depth(inp, depth):
+    """The frames' depth images [F,H,W] fp32 of a make_scene_gt_inputs scene from its instances' image-window depths ``depth`` [N,H,W], made as
+    ``bop_test_depth`` makes the test images of VSD: the nearest surface per frame in front of a background plane, an occluder 0.1 m in front of
+    the left half of instance 10, a 5 x 4 block of zero holes from the centre of instance 8's box, +-2 mm of hash noise."""
+    return bop_test_depth(inp, depth)

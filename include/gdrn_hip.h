@@ -974,6 +974,42 @@ int gdrn_model_fps(const double* pts, const int* npts, const int* npts_host, int
                    void* stream);
 int gdrn_model_diameter(const double* pts, const int* npts, const int* npts_host, int C, int n_max, double* max_sq, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scene ground truth on the device (added within ABI 5: new entry points, nothing changed): the per-instance annotations the BOP toolkit writes in
+ * an offline pass and every dataset file reads (core/gdrn_modeling/datasets/lm_pbr.py:143-178) -- mask, mask_visib and the records of
+ * scene_gt_info.json -- from depth renders that are already on the device, for N instances in F frames per call.  Units: metres and pixels.
+ * Counts are integers, bounds integer minima / maxima: no floating-point atomics, repeated calls give the same bits, and a row's result does not
+ * depend on the other rows of the call (composed scene depth apart, which is a minimum over the frame's rows and so independent of their order).
+ *
+ * gdrn_scene_gt_canvas: canvas [N][H + 2 pad_y][W + 2 pad_x] fp32, the instance rendered with a margin round the image (gdrn_render_depth with
+ *   cx + pad_x, cy + pad_y; 0 = nothing); the image is the central H x W window.  depth [N][H][W] = the window, copied;  px_count_all [N] = the
+ *   canvas pixels != 0;  bbox_obj [N][4] = the inclusive bounds x1, y1, x2, y2 of those pixels in IMAGE coordinates (negative / beyond W - 1,
+ *   H - 1 outside the image), left as a running minimum / maximum for gdrn_scene_gt_visibility to finish.  Counters are cleared inside the call.
+ * gdrn_scene_gt_compose: depth_scene [F][H][W] = per frame and pixel the smallest non-zero value of depth [N][H][W] over the frame's instances
+ *   inst[inst_off[f] .. inst_off[f + 1]) (a CSR table: inst_off [F + 1], inst [N], int32, device, with host copies that are checked: inst_off_host
+ *   starts at 0, does not decrease and ends at N, every inst_host within [0, N)); 0 where none has a value and for a frame without instances.
+ * gdrn_scene_gt_visibility: depth [N][H][W] as written by gdrn_scene_gt_canvas;  depth_scene [F][H][W] fp32 (0 = no measurement);  frame [N] and
+ *   frame_host as in gdrn_vsd;  K [N][3][3] fp64 of the IMAGE, read as fx, cx, fy, cy (no skew), as in gdrn_vsd.  Per pixel of the window:
+ *     mask       = depth != 0
+ *     dist       = sqrt((X d)^2 + (Y d)^2 + d^2) in fp64 for d = depth and d = depth_scene[frame] (misc.depth_im_to_dist_im_fast, as in gdrn_vsd)
+ *     mask_visib = GDRN_VISIB_BOP19: ((float)dist_gt - (float)dist_scene <= (float)delta  or  dist_scene == 0)  and  dist_gt > 0
+ *                  GDRN_VISIB_BOP18: dist_gt > 0  and  dist_scene > 0  and  (float)dist_gt - (float)dist_scene <= (float)delta
+ *                  (visibility._estimate_visib_mask, lib/pysixd/visibility.py:29-36)
+ *   mask, mask_visib [N][H][W] u8 (0 / 1);  px_count_valid [N] = mask and depth_scene > 0;  px_count_visib [N] = mask_visib;  bbox_visib [N][4] =
+ *   the inclusive bounds of mask_visib;  then, per instance, with px_count_all and bbox_obj of gdrn_scene_gt_canvas (same stream): a box without
+ *   pixels becomes (0, 0, -1, -1);  visib_fract [N] fp64 = px_count_visib / px_count_all as one fp64 division, 0.0 when px_count_all == 0.
+ * Status: GDRN_ERR_ARG for a NULL pointer, N / F / H / W < 1, a negative margin, a side or margin above 2^20, a frame or CSR entry out of range, a
+ *   negative or NaN delta or an unknown mode;  GDRN_ERR_SHAPE for a canvas of 2^31 - 2048 pixels and more or N / F > 65535.  Everything is checked
+ *   on the host before a stream or a device pointer is touched.  No call allocates or reads anything back. */
+enum { GDRN_VISIB_BOP19 = 0, GDRN_VISIB_BOP18 = 1 };
+int gdrn_scene_gt_canvas(const float* canvas, int N, int H, int W, int pad_x, int pad_y, float* depth, int* px_count_all, int* bbox_obj,
+                         void* stream);
+int gdrn_scene_gt_compose(const float* depth, const int* inst_off, const int* inst_off_host, const int* inst, const int* inst_host, int F, int N,
+                          int H, int W, float* depth_scene, void* stream);
+int gdrn_scene_gt_visibility(const float* depth, const float* depth_scene, const int* frame, const int* frame_host, int F, const double* K, int N,
+                             int H, int W, double delta, int visib_mode, unsigned char* mask, unsigned char* mask_visib, const int* px_count_all,
+                             int* px_count_valid, int* px_count_visib, int* bbox_obj, int* bbox_visib, double* visib_fract, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
