@@ -3,7 +3,8 @@
 //   an OpenGL render of the object's depth under the ground-truth pose                      -> gdrn_render_depth
 //   misc.calc_xyz_bp_fast(depth, R, t, K) (lib/pysixd/misc.py:288-316) + mask2bbox_xyxy     -> gdrn_xyz_from_depth
 //   (lib/utils/mask_utils.py:39-44), the "not visible" record of the tool's :142-150
-// -- for a whole batch of instances per call.  The rasterizer's rules are geometric and stated in include/gdrn_hip.h: integer-pixel rays
+// -- for a whole batch of instances per call; and the same walk with 64-bit keys, depth bits above the winning face's index, for the shaded
+// renderer (shade.hip) -> gdrn_render_visibility.  The rasterizer's rules are geometric and stated in include/gdrn_hip.h: integer-pixel rays
 // d = K^-1 [x, y, 1], coverage from the signs of d . (p x q) per edge (no perspective divide, inclusive edges, both windings), depth from the
 // ray-plane intersection, all of it fp64 with one rounding to fp32, the nearest fragment kept by an unsigned atomic min on the fp32 bits.
 //
@@ -16,6 +17,8 @@
 
 #pragma clang fp contract(off)
 
+#include "raster64.h"
+
 namespace {
 
 constexpr int RD_THREADS = 256;                 // faces per workgroup: one lane sets up one triangle
@@ -25,8 +28,6 @@ constexpr unsigned RD_INF_BITS = 0x7f800000u;   // +inf: the cleared depth buffe
 constexpr int RD_MAX_SPLIT = 16;
 constexpr int RD_TARGET_WGS = 1024;             // (4 per CU) below this many workgroups the tile walk of the large triangles is split further
 
-struct Cam { double fx, sk, cx, fy, cy; };      // K = [[fx, sk, cx], [0, fy, cy], [0, 0, 1]]
-
 // what a fragment needs of its triangle (sorted vertices a < b < c by index): the three edge normals a x b, b x c, a x c (ascending pairs), the plane
 // normal n = (b - a) x (c - a), n . a, and the clipped screen box
 struct Tri {
@@ -34,20 +35,11 @@ struct Tri {
     int x0, y0, x1, y1, face, pad_;
 };
 
-__device__ __forceinline__ Cam load_cam(const double* K) { return Cam{K[0], K[1], K[2], K[4], K[5]}; }
-
-__device__ __forceinline__ V3 cross(V3 p, V3 q) {
-    return V3{p.y * q.z - p.z * q.y, p.z * q.x - p.x * q.z, p.x * q.y - p.y * q.x};
-}
-
-// the ray of pixel (x, y): K^-1 [x, y, 1] for the upper-triangular K, third component exactly 1
-__device__ __forceinline__ void pixel_ray(const Cam& c, int x, int y, double& dx, double& dy) {
-    dy = ((double)y - c.cy) / c.fy;
-    dx = (((double)x - c.sk * dy) - c.cx) / c.fx;
-}
-
-// One fragment: coverage, depth, depth test.  `buf` is the instance's H x W slice as fp32 bit patterns.
-__device__ __forceinline__ void fragment(const Tri& T, const Cam& cam, int x, int y, int W, double far, unsigned* __restrict__ buf) {
+// One fragment: coverage, depth, depth test.  `buf` is the instance's H x W slice: fp32 bit patterns (Key = unsigned, gdrn_render_depth) or
+// visibility keys (Key = unsigned long long, gdrn_render_visibility: the same bits in the upper half, the face index within the class below them --
+// the smallest key is the nearest fp32 depth and, among equal depths, the lowest face index).  Everything up to the store is the same code.
+template <typename Key>
+__device__ __forceinline__ void fragment(const Tri& T, const Cam& cam, int x, int y, int W, double far, Key* __restrict__ buf) {
     double dx, dy;
     pixel_ray(cam, x, y, dx, dy);
     const double w0 = fma(dx, T.e0x, fma(dy, T.e0y, T.e0z));        // d . (a x b)
@@ -61,12 +53,19 @@ __device__ __forceinline__ void fragment(const Tri& T, const Cam& cam, int x, in
     if (z > far) return;
     const float zf = (float)z;                                      // the one rounding
     if (!(zf > 0.f && zf < INFINITY)) return;                       // the unsigned order of the bits is the order of the values for positive floats only
-    atomicMin(buf + (size_t)y * W + x, __float_as_uint(zf));
+    if constexpr (sizeof(Key) == 8) atomicMin(buf + (size_t)y * W + x, ((Key)__float_as_uint(zf) << 32) | (Key)(unsigned)T.face);
+    else atomicMin(buf + (size_t)y * W + x, __float_as_uint(zf));
 }
 
 __global__ __launch_bounds__(RD_THREADS) void render_clear_kernel(unsigned* __restrict__ buf, size_t n) {
     const size_t i = (size_t)blockIdx.x * RD_THREADS + threadIdx.x;
     if (i < n) buf[i] = RD_INF_BITS;
+}
+
+// the cleared visibility buffer: ~0, which is also what a pixel without a fragment keeps (no resolve pass)
+__global__ __launch_bounds__(RD_THREADS) void render_clear_keys_kernel(unsigned long long* __restrict__ buf, size_t n) {
+    const size_t i = (size_t)blockIdx.x * RD_THREADS + threadIdx.x;
+    if (i < n) buf[i] = ~0ull;
 }
 
 __global__ __launch_bounds__(RD_THREADS) void render_resolve_kernel(unsigned* __restrict__ buf, size_t n) {
@@ -79,12 +78,13 @@ __global__ __launch_bounds__(RD_THREADS) void render_resolve_kernel(unsigned* __
 // lane = pixel; a triangle's tiles are dealt round-robin to the RD_WAVES * gridDim.z waves that hold this chunk, by a rule of (face, tile)
 // alone -- the order in which a workgroup's queue fills differs from workgroup to workgroup.  The depth test is an
 // atomic min and a fragment's value does not depend on who computes it, so every distribution gives the same bits.
+template <typename Key>
 __global__ __launch_bounds__(RD_THREADS) void render_raster_kernel(const double* __restrict__ verts, const int* __restrict__ faces,
                                                                    const int* __restrict__ vert_off, const int* __restrict__ nverts,
                                                                    const int* __restrict__ face_off, const int* __restrict__ nfaces, int C,
                                                                    const int* __restrict__ labels, const double* __restrict__ Rm,
                                                                    const double* __restrict__ tv, const double* __restrict__ Km, int H, int W,
-                                                                   double near, double far, unsigned* __restrict__ depth) {
+                                                                   double near, double far, Key* __restrict__ depth) {
     __shared__ Tri queue[RD_THREADS];
     __shared__ int nqueue;
     const int i = blockIdx.x, chunk = blockIdx.y, split = blockIdx.z, tid = threadIdx.x;
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(RD_THREADS) void render_raster_kernel(const double*
 #pragma unroll
     for (int k = 0; k < 3; ++k) t[k] = tv[(size_t)i * 3 + k];
     const Cam cam = load_cam(Km + (size_t)i * 9);
-    unsigned* buf = depth + (size_t)i * H * W;
+    Key* buf = depth + (size_t)i * H * W;
 
     const int f = chunk * RD_THREADS + tid;
     bool small = false;
@@ -255,31 +255,61 @@ bool frame_fits(int N, int H, int W) {
     return hw <= 0x7fffffffLL - RD_THREADS && (long long)N * ((hw + RD_THREADS - 1) / RD_THREADS) <= 0x7fffffffLL;
 }
 
+// the argument rules the two rasterizer entry points share; `out` is the depth or the visibility buffer
+int raster_args(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off, const int* nfaces, int C, int f_max,
+                const int* labels, const int* labels_host, const double* R, const double* t, const double* K, int N, int H, int W, double near,
+                double far, const void* out) {
+    if (!verts || !faces || !vert_off || !nverts || !face_off || !nfaces || !labels || !labels_host || !R || !t || !K || !out) return GDRN_ERR_ARG;
+    if (!frame_ok(N, H, W) || C <= 0 || f_max <= 0 || !(near > 0.0) || !(near < far)) return GDRN_ERR_ARG;
+    if (!host_in_range(labels_host, N, C)) return GDRN_ERR_ARG;
+    if (!frame_fits(N, H, W) || cdiv(f_max, RD_THREADS) > 65535) return GDRN_ERR_SHAPE;
+    return GDRN_OK;
+}
+
+// few workgroups (few instances of small meshes: their triangles are the large ones): split the tile walk further
+int raster_split(int N, int chunks) {
+    const long long wgs = (long long)N * chunks;
+    int split = 1;
+    if (wgs < RD_TARGET_WGS) split = (int)((RD_TARGET_WGS + wgs - 1) / wgs);
+    return split > RD_MAX_SPLIT ? RD_MAX_SPLIT : split;
+}
+
 }  // namespace
 
 extern "C" int gdrn_render_depth(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off,
                                  const int* nfaces, int C, int f_max, const int* labels, const int* labels_host, const double* R,
                                  const double* t, const double* K, int N, int H, int W, double near, double far, float* depth, void* stream) {
-    if (!verts || !faces || !vert_off || !nverts || !face_off || !nfaces || !labels || !labels_host || !R || !t || !K || !depth) return GDRN_ERR_ARG;
-    if (!frame_ok(N, H, W) || C <= 0 || f_max <= 0 || !(near > 0.0) || !(near < far)) return GDRN_ERR_ARG;
-    if (!host_in_range(labels_host, N, C)) return GDRN_ERR_ARG;
+    const int bad = raster_args(verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far, depth);
+    if (bad != GDRN_OK) return bad;
     const int chunks = cdiv(f_max, RD_THREADS);
-    if (!frame_fits(N, H, W) || chunks > 65535) return GDRN_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const size_t n = (size_t)N * H * W;
     const unsigned blocks = (unsigned)((n + RD_THREADS - 1) / RD_THREADS);
     unsigned* bits = reinterpret_cast<unsigned*>(depth);
-    // few workgroups (few instances of small meshes: their triangles are the large ones): split the tile walk further
-    const long long wgs = (long long)N * chunks;
-    int split = 1;
-    if (wgs < RD_TARGET_WGS) split = (int)((RD_TARGET_WGS + wgs - 1) / wgs);
-    if (split > RD_MAX_SPLIT) split = RD_MAX_SPLIT;
     GDRN_LAUNCH(render_clear_kernel, dim3(blocks), dim3(RD_THREADS), 0, st, bits, n);
     GDRN_CHECK_LAUNCH();
-    GDRN_LAUNCH(render_raster_kernel, dim3(N, chunks, split), dim3(RD_THREADS), 0, st, verts, faces, vert_off, nverts, face_off, nfaces, C, labels,
-                R, t, K, H, W, near, far, bits);
+    GDRN_LAUNCH(render_raster_kernel<unsigned>, dim3(N, chunks, raster_split(N, chunks)), dim3(RD_THREADS), 0, st, verts, faces, vert_off, nverts,
+                face_off, nfaces, C, labels, R, t, K, H, W, near, far, bits);
     GDRN_CHECK_LAUNCH();
     GDRN_LAUNCH(render_resolve_kernel, dim3(blocks), dim3(RD_THREADS), 0, st, bits, n);
+    GDRN_CHECK_LAUNCH();
+    return GDRN_OK;
+}
+
+// The rasterizer's walk with 64-bit keys: one pass, one 64-bit unsigned atomic min per fragment.
+extern "C" int gdrn_render_visibility(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off,
+                                      const int* nfaces, int C, int f_max, const int* labels, const int* labels_host, const double* R,
+                                      const double* t, const double* K, int N, int H, int W, double near, double far, unsigned long long* vis,
+                                      void* stream) {
+    const int bad = raster_args(verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far, vis);
+    if (bad != GDRN_OK) return bad;
+    const int chunks = cdiv(f_max, RD_THREADS);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t n = (size_t)N * H * W;
+    GDRN_LAUNCH(render_clear_keys_kernel, dim3((unsigned)((n + RD_THREADS - 1) / RD_THREADS)), dim3(RD_THREADS), 0, st, vis, n);
+    GDRN_CHECK_LAUNCH();
+    GDRN_LAUNCH(render_raster_kernel<unsigned long long>, dim3(N, chunks, raster_split(N, chunks)), dim3(RD_THREADS), 0, st, verts, faces, vert_off,
+                nverts, face_off, nfaces, C, labels, R, t, K, H, W, near, far, vis);
     GDRN_CHECK_LAUNCH();
     return GDRN_OK;
 }

@@ -838,3 +838,86 @@ def scene_gt_depth(inp, depth):
     ``bop_test_depth`` makes the test images of VSD: the nearest surface per frame in front of a background plane, an occluder 0.1 m in front of
     the left half of instance 10, a 5 x 4 block of zero holes from the centre of instance 8's box, +-2 mm of hash noise."""
     return bop_test_depth(inp, depth)
+
+
+# ----------------------------------------------------------------------------------------------
+# scenes of the shaded renderer (gdrnet_amd.shade; the oracle is tests/shade_host.py, no golden)
+# ----------------------------------------------------------------------------------------------
+SHADE_SEEDS = {"cube": RENDER_SEEDS["cube"], "sphere": RENDER_SEEDS["sphere"], "watertight": RENDER_SEEDS["watertight"], "scene": 181}
+# ^ cube, sphere and watertight reuse the geometry (and so the accepted seeds) of make_render_inputs; tests/test_shade_cpu.py asserts for all four
+#   that no pixel centre sits within 1e-6 px of an edge without being exactly on it
+SHADE_CASES = ("cube", "sphere", "watertight", "scene")
+SHADE_PHONG = (0.4, 0.8, 0.3)         # gdrnet_amd.shade.PHONG / LIGHT (kept apart: this module imports nothing of the package)
+SHADE_LIGHT = (0.4, -0.4, -0.4)
+SHADE_SCENE_KINDS = {"sphere_in_front": 0, "tie_first": 1, "rectangle_behind": 2, "tie_second": 3, "truncated": 4, "outside": 5, "behind_camera": 6}
+
+
+def make_shade_inputs(case, seed=None):
+    """Scenes of the shaded renderer, fp64, metres: dict(vertices, faces, colors (one entry per class; floats in [0, 1] or u8), labels, frame,
+    num_frames, R, t, K (per instance), H, W, near, far, light [F,3], phong [F,3], background [F,H,W,3] u8, seed).
+
+    "cube"        the cube scene of make_render_inputs: 48 x 64, 4 poses, one per frame, skewed K; a distinct colour per vertex, large triangles
+    "sphere"      the perturbed icosphere (1280 faces), 96 x 128, the same pose in 3 frames: the default light and weights | a light behind the
+                  object (the diffuse clamp) | weights that saturate (the clamp at 1)
+    "watertight"  the exact rectangle scene, 64 x 64: every pixel centre on an edge or a vertex, exact depth ties between faces; u8 colours
+    "scene"       47 x 61 (a ragged last wave), 3 frames, 7 instances in mixed input order (SHADE_SCENE_KINDS).  Frame 0: a sphere in front of
+                  a rectangle, a cube truncated by the right and bottom border.  Frame 1: two coincident rectangles of different colour (two
+                  classes with the same geometry: an exact tie between instances), a cube outside the frame, a sphere behind the camera.
+                  Frame 2: no instance."""
+    if case not in SHADE_CASES:
+        raise ValueError(case)
+    seed = SHADE_SEEDS[case] if seed is None else seed
+    u = lambda tag, *shape: hash_uniform(seed, tag, shape)  # noqa: E731
+    if case != "scene":
+        inp = make_render_inputs(case, seed)
+        v, H, W = inp["vertices"][0], inp["H"], inp["W"]
+    if case == "cube":
+        F = 4
+        frame = np.arange(4, dtype=np.int64)
+        colors = [0.15 + 0.6 * (v / 0.1 + 0.5) + 0.1 * u("col", 8, 3)]   # the corners of a colour cube, jittered: all distinct, far apart
+        light, phong = np.tile(SHADE_LIGHT, (F, 1)), np.tile(SHADE_PHONG, (F, 1))
+        inp = dict(inp, faces=[inp["faces"][0][:, ::-1].copy()])   # mesh_cube winds clockwise seen from outside: reversed, the normals point outward
+    elif case == "sphere":
+        F = 3
+        inp = dict(inp, labels=np.zeros(F, dtype=np.int64), R=np.repeat(inp["R"], F, axis=0), t=np.repeat(inp["t"], F, axis=0),
+                   K=np.repeat(inp["K"], F, axis=0))
+        frame = np.arange(F, dtype=np.int64)
+        colors = [0.2 + 0.7 * u("col", len(v), 3)]
+        light = np.stack([np.array(SHADE_LIGHT), inp["t"][0] + np.array([0.05, -0.03, 0.5]), np.array(SHADE_LIGHT)])
+        phong = np.array([SHADE_PHONG, SHADE_PHONG, (1.5, 2.0, 1.0)])
+    elif case == "watertight":
+        F = 1
+        frame = np.zeros(1, dtype=np.int64)
+        colors = [np.floor(256.0 * u("col", len(v), 3)).astype(np.uint8)]
+        light, phong = np.array([SHADE_LIGHT]), np.array([SHADE_PHONG])
+    else:
+        H, W, F, N = 47, 61, 3, 7
+        rv, rf = mesh_rectangle(8, 8)
+        rv = rv * np.array([0.12, 0.09, 1.0])
+        sv, sf = mesh_icosphere(3, 0.05, 0.35, seed)
+        cv, cf = mesh_cube(0.1)
+        cf = cf[:, ::-1].copy()   # (outward normals, as in "cube")
+        meshes = [(sv, sf), (rv, rf), (rv.copy(), rf.copy()), (cv, cf)]
+        colors = [0.2 + 0.7 * u("col0", len(sv), 3), np.floor(40 + 200.0 * u("col1", len(rv), 3)).astype(np.uint8),
+                  np.clip(np.array([0.9, 0.2, 0.1]) + 0.1 * (u("col2", len(rv), 3) - 0.5), 0.0, 1.0), 0.15 + 0.6 * (cv / 0.1 + 0.5) + 0.1 * u("col3", 8, 3)]
+        labels = np.array([0, 1, 1, 2, 3, 3, 0], dtype=np.int64)
+        frame = np.array([0, 1, 0, 1, 0, 1, 1], dtype=np.int64)
+        K1 = np.array([[70.0, 0.0, 30.3], [0.0, 71.0, 23.4], [0.0, 0.0, 1.0]])
+        R = _random_rotations(seed, "R", N)
+        for i in (1, 2):   # the rectangles: roughly facing the camera, their normal (the winding's +z) turned towards it
+            ax = hash_normal(seed, f"tilt{i}", (1, 3))
+            R[i] = _axis_angle(ax / np.linalg.norm(ax), np.array([25.0]))[0] @ np.diag([1.0, -1.0, -1.0])
+        R[3] = R[1]
+        #                    0           1           2           3           4           5            6
+        centre = np.array([[20., 20.], [36., 24.], [29., 23.], [36., 24.], [58., 38.], [400., 20.], [30., 22.]])
+        z = np.array([0.40, 0.50, 0.55, 0.50, 0.45, 0.50, -0.50]) + 0.01 * u("t_z", 1)[0]
+        centre = centre + (u("t_px", N, 2) - 0.5)
+        centre[3] = centre[1]
+        K = np.repeat(K1[None], N, axis=0)
+        t = np.stack([(centre[:, 0] - K[:, 0, 2]) / K[:, 0, 0] * z, (centre[:, 1] - K[:, 1, 2]) / K[:, 1, 1] * z, z], axis=1)
+        inp = dict(vertices=[m[0] for m in meshes], faces=[m[1] for m in meshes], labels=labels, R=R, t=t, K=K, H=H, W=W, near=0.01, far=6.5)
+        light = np.array([SHADE_LIGHT, (-0.3, -0.2, -0.1), (0.0, 0.0, 0.0)])
+        phong = np.array([SHADE_PHONG, (0.5, 0.7, 0.4), SHADE_PHONG])
+    background = np.floor(256.0 * u("background", F, H, W, 3)).astype(np.uint8)
+    return dict(vertices=inp["vertices"], faces=inp["faces"], colors=colors, labels=inp["labels"], frame=frame, num_frames=F, R=inp["R"], t=inp["t"],
+                K=inp["K"], H=H, W=W, near=inp["near"], far=inp["far"], light=light, phong=phong, background=background, seed=seed)

@@ -1010,6 +1010,49 @@ int gdrn_scene_gt_visibility(const float* depth, const float* depth_scene, const
                              int H, int W, double delta, int visib_mode, unsigned char* mask, unsigned char* mask_visib, const int* px_count_all,
                              int* px_count_valid, int* px_count_visib, int* bbox_obj, int* bbox_visib, double* visib_fract, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Shaded colour frames of posed meshes (added within ABI 5: new entry points, nothing changed): what the reference draws with
+ * lib/meshrenderer/meshrenderer_phong.py (render, render_many) and shader/depth_shader_phong.{vs,frag} -- vertex-colour Phong shading and a z-test
+ * between several posed objects in one image -- for N instances in F frames per call, in two passes.  Mesh table, labels, R, t, K as for
+ * gdrn_render_depth; normals and colors [sum nverts][3] fp64, packed like verts (unit normals in model coordinates, colours in [0, 1]).
+ *
+ * gdrn_render_visibility: the arguments and EVERY rule of gdrn_render_depth (rays, coverage, fp64 arithmetic, the one rounding to fp32, dropped
+ *   geometry, both windings, the frame): the same fragment code with another store.  vis [N][H][W] uint64:
+ *     key = (bits of the fp32 depth << 32) | face index within the class;   ~0 where nothing is drawn
+ *   The smallest key wins (one 64-bit unsigned atomic min per fragment): the nearest fp32 depth and, among equal depths, the lowest face index.
+ *   The upper halves are bit for bit what gdrn_render_depth writes for the same inputs (0xffffffff where it writes 0).
+ * gdrn_shade_frames: one thread per frame pixel (x, y) of frame f; the instances of the frame are inst[inst_off[f] .. inst_off[f + 1]), the CSR
+ *   table of gdrn_scene_gt_compose with its host copies, checked the same way.  light [F][3] fp64: the light's position in camera coordinates
+ *   (OpenCV convention: x right, y down, z forward; metres);  phong [F][3] fp64 = (ambient, diffuse, specular) weights;  background (nullable)
+ *   [F][H][W][3] u8.  Everything below is fp64, contraction off:
+ *     instance       among the frame's instances the smallest fp32 depth (upper half of the key); equal depths go to the first in input order
+ *     geometry       the winning face's camera-space vertices a, b, c (vertex indices sorted ascending) as the rasterizer computes them, the
+ *                    pixel's ray d, z = (n.a) / (n.d) in fp64 (NOT the fp32 depth), P = z d
+ *     interpolation  perspective-correct, from the rasterizer's own edge values: the weight of a = d.(b x c), of b = d.(c x a), of c = d.(a x b),
+ *                    each divided by the sum of the three; colour and normal are interpolated with them
+ *     lighting       N = normalize(R n_interp), the zero vector if its length is 0;  L = normalize(light - P);  V = normalize(-P);
+ *                    diff = max(N.L, 0);  Rv = 2 (N.L) N - L;  spec = max(Rv.V, 0), not gated on N.L > 0 (depth_shader_phong.frag:20-26);
+ *                    rgb_k = min(1, (ambient + diffuse diff + specular spec) c_k)  (:29-35);  q_k = floor(255 rgb_k + 0.5)
+ *   rgb [F][H][W][3] u8 in the channel order of the colour table;  depth [F][H][W] fp32, the winning key's upper half, 0 where nothing is drawn;
+ *   index [F][H][W] int32 = the winning instance's row in the batch, -1 where nothing is drawn;  face (nullable) [F][H][W] int32, the winning
+ *   face, -1 where nothing is drawn;  normal_map (nullable) [F][H][W][3] u8 = floor(255 (0.5 N + 0.5) + 0.5) (depth_shader_phong.frag:36), 0
+ *   where nothing is drawn.  Where nothing is drawn rgb is the background's pixel, 0 without one; a frame without instances is its background.
+ *   A key whose face lies outside the table (not written by gdrn_render_visibility) counts as nothing drawn.
+ *   rgb, normal_map and background are 4-byte aligned: the 3-byte maps move as aligned dwords, three lanes of four one dword each.
+ *   N == 0 is allowed (every frame is its background; the per-instance pointers are then not read).
+ * Status: GDRN_ERR_ARG for a NULL pointer that is not nullable, F / H / W / C < 1, N < 0, a label or CSR entry out of range, a misaligned byte
+ *   map;  GDRN_ERR_SHAPE for H * W or the workgroup count beyond an int.  Everything is checked on the host before the launch.  Neither call
+ *   needs scratch memory beyond vis or reads anything back; no floating-point atomics, repeated calls give the same bits. */
+int gdrn_render_visibility(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off, const int* nfaces,
+                           int C, int f_max, const int* labels, const int* labels_host, const double* R, const double* t, const double* K, int N,
+                           int H, int W, double near, double far, unsigned long long* vis, void* stream);
+int gdrn_shade_frames(const unsigned long long* vis, const double* verts, const int* faces, const int* vert_off, const int* nverts,
+                      const int* face_off, const int* nfaces, const double* normals, const double* colors, int C, const int* labels,
+                      const int* labels_host, const double* R, const double* t, const double* K, const int* inst_off, const int* inst_off_host,
+                      const int* inst, const int* inst_host, int F, int N, int H, int W, const double* light, const double* phong,
+                      const unsigned char* background, unsigned char* rgb, float* depth, int* index, int* face, unsigned char* normal_map,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
