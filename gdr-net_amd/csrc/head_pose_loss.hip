@@ -968,9 +968,18 @@ __global__ __launch_bounds__(256) void pose_loss_kernel(const gdrn_pose_params p
         const float px = pt[0], py = pt[1], pz = pt[2];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const float e = sR[a * 3] * px + sR[a * 3 + 1] * py + sR[a * 3 + 2] * pz;
-            const float g = sG[a * 3] * px + sG[a * 3 + 1] * py + sG[a * 3 + 2] * pz;
-            const float d = w * e - w * g;
+            // A prediction bit-equal to its target must give d == 0 exactly (|.| has gradient 0 there; sgn of a rounding residue is a full-magnitude
+            // gradient with arbitrary signs).  So (1) e and g are the SAME operations in the same order: written as sums of products, the compiler
+            // contracted a x + b y into fma(a, x, b y) for one and fma(b, y, a x) for the other; (2) w e and w g stay two rounded products, as in the
+            // reference (pm_loss.py: w * est - w * tgt), instead of fma(w, e, -(w g)), which leaves the rounding residue of w g.
+            const float e = fmaf(sR[a * 3 + 2], pz, fmaf(sR[a * 3 + 1], py, sR[a * 3] * px));
+            const float g = fmaf(sG[a * 3 + 2], pz, fmaf(sG[a * 3 + 1], py, sG[a * 3] * px));
+            float d;
+            {
+#pragma clang fp contract(off)
+                const float we = w * e, wg = w * g;
+                d = we - wg;
+            }
             acc[0] += fabsf(d);
             const float s = sgn(d) * w;
             acc[1 + a * 3 + 0] += s * px;
@@ -1245,7 +1254,8 @@ extern "C" int gdrn_pose_loss(const gdrn_pose_params* p, void* stream) {
         return GDRN_ERR_ARG;
     if (p->fc2_ws && (!p->fc2_bias || !p->f2_out || !p->w_rt || !p->b_rt || !p->fc_w || p->fc2_splits <= 0)) return GDRN_ERR_ARG;
     if (p->dfc_comb && (!p->gw || !p->train)) return GDRN_ERR_ARG;
-    if (p->losses && !p->loss_rows && hipMemsetAsync(p->losses, 0, 3 * sizeof(float), ST) != hipSuccess) return GDRN_ERR_LAUNCH;
+    if (p->sym && p->Kmax < 1) return GDRN_ERR_ARG;   // (the candidate rows are indexed n * Kmax + s)
+    if (p->train && p->losses && !p->loss_rows && hipMemsetAsync(p->losses, 0, 3 * sizeof(float), ST) != hipSuccess) return GDRN_ERR_LAUNCH;
     GDRN_LAUNCH(pose_loss_kernel, dim3(p->N), dim3(256), 0, ST, *p);
     GDRN_CHECK_LAUNCH();
     return GDRN_OK;

@@ -402,7 +402,7 @@ int gdrn_head_tail_bwd(const float* head, int hs, const void* pnp_in, const void
  *   point-matching loss (pm_loss.py:82-114, misc.py:930-949, symmetric: pose_utils.py:430-482),
  *   centroid / z L1 (GDRN.py:444-471).
  * fc: fp32 [N][fs] rows = (rot6d[6], t_[3]).  sym: fp32 [N][Kmax][9] + sym_count[N] (NULL: none).
- * outputs: rot [N][9], trans [N][3]; losses[3] = (loss_PM_R, loss_centroid, loss_z) (zeroed inside);
+ * outputs: rot [N][9], trans [N][3]; losses[3] = (loss_PM_R, loss_centroid, loss_z) (train mode: zeroed inside; test mode: not touched);
  * dfc: fp32 [3][N][fs] unit gradients d loss_k / d fc (NULL in test mode); vis: fp32 [N][2] per-RoI
  * rotation error (deg) / translation error. */
 typedef struct gdrn_pose_params {
