@@ -26,7 +26,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void head_tail_fwd_kernel(const float* __restrict__ head, int hs,
                                                             const float* __restrict__ coord2d,
                                                             const float* __restrict__ extents, T* __restrict__ pnp, int pcs,
-                                                            int N, int HW, int nreg) {
+                                                            int N, int HW, int nreg, int write_pad) {
     const int q = threadIdx.x & 15;
     const long long M = (long long)N * HW;
     const long long g0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
@@ -54,7 +54,8 @@ __global__ __launch_bounds__(256) void head_tail_fwd_kernel(const float* __restr
             if (q + 16 * j < nreg) st1<T>(o + 5 + q + 16 * j, e[j] / se);
         if (q < 3) st1<T>(o + q, (h[1 + q] - 0.5f) * extents[n * 3 + q]);
         else if (q < 5) st1<T>(o + q, coord2d[((size_t)n * 2 + (q - 3)) * HW + pix]);
-        for (int c = 5 + nreg + q; c < pcs; c += 16) st1<T>(o + c, 0.f);
+        if (write_pad)   // (GDRN_PREZEROED: the pad channels are the caller's, as on the 64-region path)
+            for (int c = 5 + nreg + q; c < pcs; c += 16) st1<T>(o + c, 0.f);
     }
 }
 
@@ -604,7 +605,7 @@ __global__ __launch_bounds__(256) void head_tail_bwd_kernel(const float* __restr
                                                             const float* __restrict__ mtr,
                                                             const long long* __restrict__ gt_region,
                                                             const double* __restrict__ acc, const float* __restrict__ gw,
-                                                            T* __restrict__ dhead, int dcs, int N, int HW, int nreg) {
+                                                            T* __restrict__ dhead, int dcs, int N, int HW, int nreg, int write_pad) {
     const int q = threadIdx.x & 15;  // 16 lanes per pixel, lane q <-> classes q + 16 j
     const long long M = (long long)N * HW;
     const long long g0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
@@ -662,7 +663,8 @@ __global__ __launch_bounds__(256) void head_tail_bwd_kernel(const float* __restr
             if (dpnp != nullptr) d += ld1<T>(dpnp + m * pcs + c) * extents[n * 3 + c];
             st1<T>(o + q, d);
         }
-        for (int c = 4 + ncls + q; c < dcs; c += 16) st1<T>(o + c, 0.f);
+        if (write_pad)
+            for (int c = 4 + ncls + q; c < dcs; c += 16) st1<T>(o + c, 0.f);
     }
 }
 
@@ -1067,9 +1069,9 @@ int launch_ht_fwd(const float* head, int hs, const float* coord2d, const float* 
                                gt_xyz, mv, mt, greg, acc, N, HW, write_pad, rows);
     } else {
         if (dt == GDRN_DT_F32)
-            GDRN_LAUNCH(head_tail_fwd_kernel<float>, dim3(blocks), dim3(256), 0, st, head, hs, coord2d, extents, (float*)pnp_in, pcs, N, HW, nreg);
+            GDRN_LAUNCH(head_tail_fwd_kernel<float>, dim3(blocks), dim3(256), 0, st, head, hs, coord2d, extents, (float*)pnp_in, pcs, N, HW, nreg, write_pad);
         else
-            GDRN_LAUNCH(head_tail_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, head, hs, coord2d, extents, (bf16_t*)pnp_in, pcs, N, HW, nreg);
+            GDRN_LAUNCH(head_tail_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, head, hs, coord2d, extents, (bf16_t*)pnp_in, pcs, N, HW, nreg, write_pad);
         if (LOSS) {
             const int lb = (int)std::min<long long>((M + 15) / 16, 2048);
             GDRN_LAUNCH(map_loss_fwd_kernel, dim3(lb), dim3(256), 0, st, head, hs, gt_xyz, mv, mt, greg, N, HW, nreg, acc, rows);
@@ -1179,7 +1181,7 @@ extern "C" int gdrn_head_tail_loss_fwd(const float* head, int hs, const float* c
 
 extern "C" int gdrn_map_loss_fwd(const float* head, int hs, const float* gt_xyz, const float* mask_visib, const float* mask_trunc,
                                  const long long* gt_region, int N, int HW, int nreg, double* acc, void* stream) {
-    if (!head || !gt_xyz || !mask_visib || !mask_trunc || !gt_region || !acc || N <= 0 || HW <= 0 || nreg < 1 || nreg > 64)
+    if (!head || !gt_xyz || !mask_visib || !mask_trunc || !gt_region || !acc || N <= 0 || HW <= 0 || nreg < 1 || nreg > 64 || hs < nreg + 5)
         return GDRN_ERR_ARG;
     if (hipMemsetAsync(acc, 0, 8 * sizeof(double), ST) != hipSuccess) return GDRN_ERR_LAUNCH;
     const long long M = (long long)N * HW;
@@ -1220,9 +1222,9 @@ extern "C" int gdrn_head_tail_bwd(const float* head, int hs, const void* pnp_in,
                                   int HW, int nreg, int dtype, void* stream) {
     const int dt = dtype & 0xff, write_pad = (dtype & GDRN_PREZEROED) ? 0 : 1;
     if (!head || !extents || !gt_xyz || !mask_visib || !mask_trunc || !gt_region || !acc || !gw || !d_head || N <= 0 ||
-        HW <= 0 || nreg < 1 || nreg > 64 || dcs < nreg + 5 || (dt != GDRN_DT_F32 && dt != GDRN_DT_H16))
-        return GDRN_ERR_ARG;
-    if (d_pnp_in != nullptr && pnp_in == nullptr) return GDRN_ERR_ARG;
+        HW <= 0 || nreg < 1 || nreg > 64 || hs < nreg + 5 || dcs < nreg + 5 || (dt != GDRN_DT_F32 && dt != GDRN_DT_H16))
+        return GDRN_ERR_ARG;   // (the kernels read h[4 + nreg])
+    if (d_pnp_in != nullptr && (pnp_in == nullptr || pcs < nreg + 5)) return GDRN_ERR_ARG;   // (... and pnp[4 + nreg], d_pnp[4 + nreg])
     const long long M = (long long)N * HW;
     const int blocks = (int)std::min<long long>((M + 15) / 16, 4096);
     const bool fast = ht64_ok(nreg, hs, dcs) && (d_pnp_in == nullptr || ht64_ok(nreg, hs, pcs));
@@ -1233,7 +1235,7 @@ extern "C" int gdrn_head_tail_bwd(const float* head, int hs, const void* pnp_in,
         else
             GDRN_LAUNCH(head_tail_bwd_kernel<float>, dim3(blocks), dim3(256), 0, ST, head, hs, (const float*)pnp_in,
                                (const float*)d_pnp_in, pcs, extents, gt_xyz, mask_visib, mask_trunc, gt_region, acc, gw,
-                               (float*)d_head, dcs, N, HW, nreg);
+                               (float*)d_head, dcs, N, HW, nreg, write_pad);
     } else {
         if (fast)
             GDRN_LAUNCH(head_tail_bwd64_kernel<bf16_t>, dim3(blocks), dim3(256), 0, ST, head, hs, (const bf16_t*)pnp_in, (const bf16_t*)d_pnp_in,
@@ -1241,7 +1243,7 @@ extern "C" int gdrn_head_tail_bwd(const float* head, int hs, const void* pnp_in,
         else
             GDRN_LAUNCH(head_tail_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, ST, head, hs, (const bf16_t*)pnp_in,
                                (const bf16_t*)d_pnp_in, pcs, extents, gt_xyz, mask_visib, mask_trunc, gt_region, acc, gw,
-                               (bf16_t*)d_head, dcs, N, HW, nreg);
+                               (bf16_t*)d_head, dcs, N, HW, nreg, write_pad);
     }
     GDRN_CHECK_LAUNCH();
     return GDRN_OK;

@@ -367,12 +367,20 @@ int gdrn_bias_grad(const void* dy, int cs, int rows, int C, float* db, int dtype
  * Head tail: slicing of the 1x1 output conv into mask / xyz / region, channel softmax over
  * region[:,1:], concat with roi_coord_2d, extent de-normalisation -> Patch-PnP input
  * (GDRN.py:156-169, conv_pnp_net.py:121-125).  head: fp32 [N*HW][hs] = (mask, x, y, z, region[nreg+1]);
- * pnp_in: dtype [N*HW][pcs], channels (xyz(3), coord2d(2), softmax(nreg), zero pad). */
+ * pnp_in: dtype [N*HW][pcs], channels (xyz(3), coord2d(2), softmax(nreg), zero pad).
+ * Rows: 1 <= nreg <= 64 and EVERY row stride an entry point takes holds a whole row -- hs >= nreg + 5, pcs >= nreg + 5, dcs >= nreg + 5
+ * (gdrn_head_tail_bwd: pcs only when d_pnp_in is given, pnp_in and d_pnp_in are not read otherwise; gdrn_map_loss_fwd: hs) -- else
+ * GDRN_ERR_ARG and nothing is written: the kernels read h[4 + nreg] and pnp[4 + nreg], with a shorter stride the next pixel's values and,
+ * in the last row, memory behind the buffer.  Columns >= nreg + 5 of head, pnp_in and d_pnp_in are never read; of d_pnp_in neither are
+ * channels 3 and 4 used (the 2-D coordinates have no gradient). */
 int gdrn_head_tail_fwd(const float* head, int hs, const float* coord2d, const float* extents, void* pnp_in, int pcs,
                        int N, int HW, int nreg, int dtype, void* stream);
 /* Train mode: gdrn_head_tail_fwd and gdrn_map_loss_fwd in ONE pass over the logits (acc as below, zeroed inside).
- * dtype | GDRN_PREZEROED (here and in gdrn_head_tail_fwd / gdrn_head_tail_bwd): the channels >= 72 of the pcs / dcs wide rows are
- * already zero and stay the caller's (the engine zero-fills its buffers once instead of re-writing 56 pad channels per pixel and step). */
+ * dtype | GDRN_PREZEROED (here and in gdrn_head_tail_fwd / gdrn_head_tail_bwd): the pad channels of the pcs / dcs wide rows are
+ * already zero and stay the caller's (the engine zero-fills its buffers once instead of re-writing 56 pad channels per pixel and step).
+ * The contract, for every region count and row stride: WITHOUT the flag every channel >= nreg + 5 of a row is written as 0; WITH it the
+ * channels from the end of the last written group on are not written at all -- >= 72 on the 64-region path (rows of whole 4-element groups:
+ * 69..71 are still written as 0), >= nreg + 5 on the generic path. */
 int gdrn_head_tail_loss_fwd(const float* head, int hs, const float* coord2d, const float* extents, void* pnp_in, int pcs,
                             const float* gt_xyz, const float* mask_visib, const float* mask_trunc, const long long* gt_region,
                             double* acc, int N, int HW, int nreg, int dtype, void* stream);
