@@ -498,7 +498,7 @@ class GDRN(nn.Module):
         eng = plan.e
         # (r6) dL/dloss_k is known BEFORE the forward pass here (unlike under autograd): written first, so that the pose kernel can leave dL/dfc
         # itself (no combine / cast launches in front of the backward pass) and the loss-finalize launch the weighted loss vector this returns
-        seam = eng.fc_tail and eng.h16 and bool(getattr(plan, "acc_rows", 0))
+        seam = eng.fc_tail and eng.h16 and bool(plan.acc_rows)
         dyn = eng.loss_scale_dev()   # fp16, dynamic loss scale: its state on the device (None: bf16 / fp32 / fp16 with a static scale)
         ls = 1.0 if dyn is not None else eng._ls_host   # static loss scale on dL/dloss, divided out where the optimizer reads the gradients
         if dyn is not None:

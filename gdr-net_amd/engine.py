@@ -128,21 +128,16 @@ class Engine:
         self.s2_halo = self.h16 and _os.environ.get("GDRN_S2_HALO", "1") != "0"
         self.s2_tw8 = _os.environ.get("GDRN_S2_TW8", "1") != "0"   # 8-wide maps on the stride-2 kernels (two images per tile); 0: the generic kernel there (A/B)
         self.fc_tail = self.h16 and _os.environ.get("GDRN_FC_TAIL", "1") != "0"   # (A/B, r6) fc2 finish + fc_r | fc_t + pose decode as one launch; seeded train step
-        self.tail_overlap = True
-        self.side_small = True
         self.wgrad_side_lds = 84 * 1024
-        self.stem_direct = self.h16
-        self.stem_wgrad = self.stem_direct
+        self.stem_direct = self.h16   # the dedicated stem kernels, forward and (fused with bn1's backward apply) weight gradient
         self.stem_w32 = torch.zeros(64 * 7 * 32, dtype=self.tdt, device=self.dev) if self.stem_direct else None
-        self.fc_splitk = True
         # BatchNorm apply passes (forward scale/shift(+residual)+ReLU, backward dx = a*g + b*x + c) evaluated by the CONSUMER halo
         # conv while it stages its input patch (gdrn_conv_params.xf_*) instead of separate launches; "0" = separate passes (A/B, tests)
         self.fuse_xf = self.h16 and _os.environ.get("GDRN_FUSE_XF", "1") != "0"
-        # which transforms are fused, by xf mode (bit m-1 = mode m) and by the largest feature-map side they are used on (bring-up / tuning)
+        # (every transform mode, on every map size: r2's policy sweep by mode and by largest feature-map side -- all-fused won)
         # BatchNorm-backward mask + sums also in the generic kernel's epilogue (1x1 output conv, stride-2 / transposed data gradients)
         self.gemm_bnb = self.h16 and _os.environ.get("GDRN_GEMM_BNB", "1") == "1"
         self.halo_waves = int(_os.environ.get("GDRN_HALO_WAVES", "0"))   # A/B: 4 / 8 force the four- / eight-wave form of the first halo kernel's 128-channel tile
-        self.xf_mask, self.xf_maxhw, self.xf_minc = 15, 64, 0   # every transform mode, on every map size (r2's policy sweep: all-fused won)
         # second-generation halo kernel (conv3x3_v3.hip): GDRN_V3 = "0" never, "2" wherever it covers the shape (the 256-channel tile also on
         # small grids) -- A/B and the plan variants of tests/test_teacher_forced_gpu.py; default: where the library measured it faster.  The
         # library itself reads no environment: the policy travels in gdrn_conv_params (w_frag of the gdrn_conv3x3_wfrag query, v3_min_wg)
@@ -157,9 +152,9 @@ class Engine:
         #  Rejected by measurement and removed from the engine in round 5 (DESIGN.md section 4 has the figures): extra cuts of the grouped
         #  launches inside a bucket, a third stream for the HBM-bound bucket tails, the 128 x 64 weight-gradient tile (the kernel stays in the
         #  library behind gdrn_wgrad_params.variant, with its kernel tests)
+        #  (extra launch groups of the grouped weight gradient were measured again in r6: no gain.  Small side-stream ops wait for their
+        #  bucket's end, Plan._merge_forks: 6 instead of 11 stream switches per backward pass -- r6: no measurable effect on the step, kept)
         self.wgrad_blocks = 768 if (self.wgrad_stream or self.wgrad_force_lds) else 1536
-        self.wgrad_cuts = ()   # extra launch groups of the grouped weight gradient (backward-group indices): measured again in r6, no gain
-        self.merge_forks = True   # small side-stream ops wait for their bucket's end: 6 instead of 11 stream switches per backward pass (r6: no measurable effect on the step)
         nb = _os.environ.get("GDRN_BUCKETS")
         self.buckets_from_env = nb is not None
         if nb is None:
@@ -173,8 +168,7 @@ class Engine:
         self.bucket_first_group, self.bucket_marks = BUCKET_LAYOUTS[int(nb)]
         self.layers = OrderedDict()
         self._versions = {}
-        self.bn_fold = {}  # bn key -> NS(scale, shift, layer): eval-mode BatchNorm folded into the preceding conv
-        self.fold_bn = True
+        self.bn_fold = {}  # bn key -> NS(scale, shift, layer): eval-mode BatchNorm folded into the preceding conv (every eval plan)
         # bumped by every training forward (running statistics changed).  Shared by the engines of one model (bn_cell; ADVICE r4: the fp16
         # inference engine of cfg.TEST.AMP_TEST must see the statistics its bf16 training twin moved through raw pointers)
         self._bn_cell = bn_cell if bn_cell is not None else [0]

@@ -1,8 +1,9 @@
 """Plans of the GDR-Net hot-path executor: static buffers + pre-bound C-ABI call lists for one (batch size, train / eval, losses)
-configuration of one Engine (engine.py).  `Plan._build` walks the fixed graph once -- stem, 16 BasicBlocks, geometric head, head tail,
-Patch-PnP, pose decode, losses (core/gdrn_modeling/models/GDRN.py:110-306, resnet_backbone.py:69-80, cdpn_rot_head_region.py:182-193,
-conv_pnp_net.py:111-157) -- and appends one closure per kernel launch to `fwd` and, group by group in reverse, to `bwd`; `run_forward` /
-`run_backward` replay them on the current HIP stream (and the engine's side stream)."""
+configuration of one Engine (engine.py).  `Plan._build` walks the fixed graph once, one stage builder per step -- stem, 16 BasicBlocks,
+geometric head, head tail, Patch-PnP, pose decode, losses (core/gdrn_modeling/models/GDRN.py:110-306, resnet_backbone.py:69-80,
+cdpn_rot_head_region.py:182-193, conv_pnp_net.py:111-157) -- and appends one closure per kernel launch to `fwd` and, group by group in
+reverse, to `bwd`; `run_forward` / `run_backward` replay them on the current HIP stream (and the engine's side stream).
+tools/plan_trace.py writes every launch of a plan with every argument as text, on the CPU: diff it across a change of this file."""
 import ctypes as C
 from types import SimpleNamespace as NS
 
@@ -11,6 +12,22 @@ import torch
 from . import cabi
 from .cabi import ACC_ROWS, PREZEROED, ConvParams, PoseParams, S2Params, S2dParams, WgradParams, check, ptr
 from .engine import HEAD_CONVS, RESNET34_LAYERS, RESNET34_PLANES, _ru
+
+F32t = torch.float32
+
+
+def _launch(fn, what, args, meta=None):
+    """a plain launch, one that reads nothing from ctx: fn(*args, stream).  Tensors among args go in as their device pointers, taken once,
+    here; the op holds on to the tensors."""
+    cargs = tuple(ptr(a) if isinstance(a, torch.Tensor) else a for a in args)
+
+    def run(st, ctx):
+        check(fn(*cargs, st), what)
+
+    run.args = args
+    if meta is not None:
+        run.meta = meta
+    return run
 
 
 def _probed(op, sink):
@@ -53,6 +70,11 @@ class Plan:
         self.generation = 0        # bumped by every run_forward: a backward checks its activations are still the plan's
         self.head_valid = True     # plan.head_out holds the logits of the last forward (False: inference without cfg.TEST.USE_PNP skipped them)
         self.grad_group = {}       # parameter name -> forward index of the backward group that completes its gradient
+        self.acc_rows, self.acc, self.losses, self.pose_rows = 0, None, None, None   # map- / pose-loss partial rows and the 8 losses (plans with losses)
+        self.fc_tail = self._fc2 = None   # (fc2 workspace, splits), (f2, fc2 bias, fc_rt layer): fc2's finish pass inside the pose launch
+        self.op_events = None      # bench.py: a list here makes run_backward bracket its conv launches with timing events
+        self._front_n = 0          # bucket-end ops placed in FRONT of the stem group (see _bucket_end)
+        self._marks = None         # _bucket_marks(), computed once
         self._build()
         if self.has_backward:
             self._finish_unpack()
@@ -63,6 +85,20 @@ class Plan:
         self.bwd = [op for g in reversed(self.bwd_groups) for op in g]
 
     # ---- op builders -------------------------------------------------------------------------
+    def _E(self, *shape, dtype=None):
+        """a plan buffer, pinned in self.keep: the pre-bound C structs hold RAW device pointers, so a buffer referenced only through them
+        would otherwise be returned to the caching allocator when the plan is built and be handed out again while the kernels still
+        write to it"""
+        t = self.e._empty(*shape, dtype=dtype)
+        self.keep.append(t)
+        return t
+
+    def _hook_fold(self):
+        """the first folded BatchNorm of an eval plan puts Engine.eval_refresh in front of the plan's eval-mode preparation"""
+        if not self._fold_hooked:
+            self.eval_prep.append(lambda st, ctx: self.e.eval_refresh())
+            self._fold_hooked = True
+
     def _conv(self, L, x, xs, y, Hi, Wi, Ho, Wo, stride, pad, mode=0, w=None, rows=None, cin=None, cout=None, x_cs=None,
               y_cs=None, bias=None, addend=None, add_cs=0, act=0, out_f32=0, stats=None, KH=None, KW=None, bnb=None, evalw=False, xf=None):
         """bnb = (bn key, raw input of that BN, stored activation or None, affine mask?): data-gradient launch whose
@@ -162,7 +198,13 @@ class Plan:
                 if s:
                     check(s, f"conv {L.key}")
 
-        # metadata for the roofline measurement in bench.py: kernel instantiation + algorithmic FLOPs
+        run.meta = self._conv_meta(L, cp, (th.value, tw.value, hbn.value) if use_halo else None, Hi, Wi, Ho, Wo, mode, w is not None)
+        return run, cp
+
+    def _conv_meta(self, L, cp, halo_tile, Hi, Wi, Ho, Wo, mode, dgrad):
+        """metadata of a _conv launch for the roofline measurement in bench.py: kernel instantiation + algorithmic FLOPs and bytes.
+        halo_tile: (th, tw, hbn) of a halo launch, None for the generic kernel; dgrad: the launch is the layer's data gradient."""
+        e, ref = self.e, C.byref(cp)
         bm, bn = C.c_int(0), C.c_int(0)
         e.lib.gdrn_conv_tile(ref, C.byref(bm), C.byref(bn))
         # true (unpadded) MACs: the layer's forward MAC count whichever direction this launch computes
@@ -171,22 +213,22 @@ class Plan:
         elif L.kind == "fc1":
             macs = self.B * L.O * L.I * L.KK
         else:
-            sp = (Ho * Wo) if (mode == 0 and (w is None or L.kind == "convT")) else (Hi * Wi)
+            sp = (Ho * Wo) if (mode == 0 and (not dgrad or L.kind == "convT")) else (Hi * Wi)
             if L.kind == "convT":
                 sp = 8 * 8  # Hin*Win*Cin*Cout*k^2
             macs = self.B * sp * L.O * L.I * L.KK
         dn = "bf16" if e.h16 else "f32"   # (the 16-bit instantiation: its name in a trace is the same in both library builds)
-        if use_halo and cp.w_frag == 2:
-            kname = f"conv3x3_v3_kernel<{th.value},{hbn.value},{'2,4,1' if hbn.value == 256 else '2,2,2'},{cp.xf_mode}>"  # (the template's name in a trace)
-        elif use_halo:
-            kname = f"conv3x3_halo_kernel<{dn},{th.value},{tw.value},{hbn.value},{cp.xf_mode},{int(e.lib.gdrn_conv3x3_halo_waves(ref)) // 4}>"
+        th, tw, hbn = halo_tile or (0, 0, 0)
+        if halo_tile and cp.w_frag == 2:
+            kname = f"conv3x3_v3_kernel<{th},{hbn},{'2,4,1' if hbn == 256 else '2,2,2'},{cp.xf_mode}>"  # (the template's name in a trace)
+        elif halo_tile:
+            kname = f"conv3x3_halo_kernel<{dn},{th},{tw},{hbn},{cp.xf_mode},{int(e.lib.gdrn_conv3x3_halo_waves(ref)) // 4}>"
         else:
             kname = f"conv_gemm_kernel<{dn},{bm.value},{bn.value}>"
         # algorithmic bytes (SURVEY 8(d) convention: activations in + out once, weights once, at the storage width)
         esz = 2 if e.h16 else 4
         nbytes = (self.B * Hi * Wi * cp.Cin + self.B * Ho * Wo * cp.Cout) * esz + cp.Cout * cp.Cin * cp.KH * cp.KW * esz
-        run.meta = dict(kernel=kname, flops=2.0 * macs, bytes=float(nbytes), layer=L.key + (":dgrad" if w is not None else ""))
-        return run, cp
+        return dict(kernel=kname, flops=2.0 * macs, bytes=float(nbytes), layer=L.key + (":dgrad" if dgrad else ""))
 
     def _s2(self, L, x, x_cs, y, Hi, Ho, Ld=None, yd=None, stats=None, stats_d=None, bias=None, bias_d=None, act=0, evalw=False):
         """forward launch of a 3x3 stride-2 conv on the parity-plane halo kernel (gdrn_conv3x3s2), with the block's 1x1 shortcut conv Ld in the
@@ -332,9 +374,7 @@ class Plan:
             return None
         if evalmode:
             f = e.fold(bnkey, LT)
-            if not self._fold_hooked:
-                self.eval_prep.append(lambda st, ctx: self.e.eval_refresh())
-                self._fold_hooked = True
+            self._hook_fold()
             sp.w, sp.bias, sp.act = ptr(LT.wfF_e), ptr(f.shift), 1
         else:
             sp.stats = ptr(stats)
@@ -393,15 +433,14 @@ class Plan:
         esz = 2 if e.h16 else 4
         run.meta = dict(kernel=kname, flops=2.0 * macs, bytes=float(self.B * (Hi * Wi * cin + Ho * Wo * cout) * esz + 4 * cout * cin * wp.KH * wp.KW),
                         layer=L.key + ":wgrad")
-        run.side = e.side_small  # feeds only the optimizer: off the data-gradient chain (side stream, see run_backward)
-        run.defer = bool(run.side and defer)
-        return run
+        return self._side(run, defer)  # feeds only the optimizer: off the data-gradient chain (side stream, see run_backward)
 
-    def _side(self, op, defer=False):
-        """mark a backward op whose result only the optimizer reads: it may run on the side stream (Engine.side_small).
+    @staticmethod
+    def _side(op, defer=False):
+        """mark a backward op whose result only the optimizer reads: it may run on the side stream.
         defer: the op may wait for the end of its gradient bucket (see _merge_forks)."""
-        op.side = self.e.side_small
-        op.defer = bool(defer and op.side)
+        op.side = True
+        op.defer = bool(defer)
         return op
 
     def _merge_forks(self):
@@ -410,7 +449,7 @@ class Plan:
         the fc layers and of the 1x1 shortcut convs of layer3.0 / layer4.0, whose buffers are their own -- move to the end of their bucket, in
         front of its grouped weight-gradient launch: one fork per bucket instead of one per op."""
         e = self.e
-        if not (e.wgrad_stream and e.merge_forks):
+        if not e.wgrad_stream:
             return
         first = list(e.bucket_first_group)
         for bkt, g0 in enumerate(first):
@@ -424,7 +463,7 @@ class Plan:
                 continue
             g = self.bwd_groups[g0]
             at = next((i for i, op in enumerate(g) if getattr(op, "bucket_end", False)), len(g))
-            if bkt == len(first) - 1 and getattr(self, "_front_n", 0):
+            if bkt == len(first) - 1 and self._front_n:
                 at = 0   # (last bucket, tail overlap: its bucket-end ops sit in FRONT of the stem group)
             g[at:at] = moved
 
@@ -466,7 +505,7 @@ class Plan:
         if L.kind == "stem":
             g = e.grads[L.src[0]]
             # (side like the weight-gradient launch whose result it reads: the two stay in order on one stream)
-            return self._side(lambda st, ctx: check(lib.gdrn_unpack_stem_w(ptr(L.dwp), ptr(g), st), "unpack_stem_w"))
+            return self._side(_launch(lib.gdrn_unpack_stem_w, "unpack_stem_w", (L.dwp, g)))
         self._unpack_pending.append((len(self.bwd_groups), L))
         return None  # marker, dropped when the groups are flattened
 
@@ -483,25 +522,19 @@ class Plan:
         if self.bn_train:
             rows = self._stats_rows(cp)
             assert rows * 2 * C_ <= stats.numel(), (bnkey, rows, C_)  # the producer's partial rows fit the scratch
-            ops.append(lambda st, ctx: check(lib.gdrn_bn_finalize(ptr(stats), rows, C_, float(npix), ptr(g), ptr(b), ptr(rm),
-                                                                  ptr(rv), ptr(nbt), 0.1, 1e-5, ptr(s.mean), ptr(s.invstd),
-                                                                  ptr(s.scale), ptr(s.shift), ptr(e.bn_ws), st), "bn_finalize"))
+            ops.append(_launch(lib.gdrn_bn_finalize, "bn_finalize", (stats, rows, C_, float(npix), g, b, rm, rv, nbt, 0.1, 1e-5, s.mean, s.invstd,
+                                                                     s.scale, s.shift, e.bn_ws)))
         else:
             # eval mode: scale/shift only depend on the parameters and running statistics -- recomputed when those changed
             # (see run_forward), not on every call (43 tiny launches = 8 % of an inference forward)
-            self.eval_prep.append(lambda st, ctx: check(lib.gdrn_bn_eval_params(ptr(g), ptr(b), ptr(rm), ptr(rv), 1e-5, C_, ptr(s.scale),
-                                                                                ptr(s.shift), st), "bn_eval_params"))
+            self.eval_prep.append(_launch(lib.gdrn_bn_eval_params, "bn_eval_params", (g, b, rm, rv, 1e-5, C_, s.scale, s.shift)))
         if y is not None:
-            ops.append(lambda st, ctx: check(lib.gdrn_bn_apply(ptr(raw), ptr(s.scale), ptr(s.shift), ptr(residual), ptr(y), npix,
-                                                               C_, relu, e.dt, st), "bn_apply"))
+            ops.append(_launch(lib.gdrn_bn_apply, "bn_apply", (raw, s.scale, s.shift, residual, y, npix, C_, relu, e.dt)))
         return ops
 
-    def _xf_ok(self, L, mode=None, hw=0):
-        """can layer L's halo launches (forward and data gradient) take a fused operand transform (of that mode, on hw x hw maps)?"""
-        e = self.e
-        if mode is not None and (not (e.xf_mask >> (mode - 1)) & 1 or hw > e.xf_maxhw or L.I < e.xf_minc):
-            return False
-        return e.fuse_xf and self.bn_train and L.kind == "conv" and L.wfF is not None and L.KK == 9 and not L.s2
+    def _xf_ok(self, L):
+        """can layer L's halo launches (forward and data gradient) take a fused operand transform?"""
+        return self.e.fuse_xf and self.bn_train and L.kind == "conv" and L.wfF is not None and L.KK == 9 and not L.s2
 
     def _bn_coef_op(self, bnkey, rows, nrows):
         """rows [nrows][2][C] of BatchNorm-backward sums -> (ka, kb, kc) of dx = ka*g + kb*x + kc, dgamma, dbeta (one launch)."""
@@ -512,15 +545,12 @@ class Plan:
         g = e.P[bnkey + ".weight"]
         dg, db = e.grads[bnkey + ".weight"], e.grads[bnkey + ".bias"]
         self.grad_group[bnkey + ".weight"] = self.grad_group[bnkey + ".bias"] = len(self.bwd_groups)
-        return lambda st, ctx: check(lib.gdrn_bn_bwd_coef(ptr(rows), nrows, s.C, s.npix, ptr(g), ptr(s.mean), ptr(s.invstd), ptr(s.ka), ptr(s.kb),
-                                                          ptr(s.kc), ptr(dg), ptr(db), st), "bn_bwd_coef")
+        return _launch(lib.gdrn_bn_bwd_coef, "bn_bwd_coef", (rows, nrows, s.C, s.npix, g, s.mean, s.invstd, s.ka, s.kb, s.kc, dg, db))
 
     def _conv_bn_eval(self, L, bnkey, x, xs, y, Hi, Wi, Ho, Wo, stride, pad, relu, residual=None, add_cs=0, **kw):
         """eval mode: conv -> BatchNorm (-> +residual) (-> ReLU) as ONE launch, y = act(conv_{w*scale}(x) + shift + residual)."""
         f = self.e.fold(bnkey, L)
-        if not self._fold_hooked:
-            self.eval_prep.append(lambda st, ctx: self.e.eval_refresh())
-            self._fold_hooked = True
+        self._hook_fold()
         op, _ = self._conv(L, x, xs, y, Hi, Wi, Ho, Wo, stride, pad, bias=f.shift, addend=residual, add_cs=add_cs, act=1 if relu else 0,
                            evalw=True, **kw)
         return op
@@ -554,15 +584,13 @@ class Plan:
             nrows = int(lib.gdrn_bn_bwd_reduce_rows(s.npix, s.C, e.dt))
             assert nrows > 0 and nrows * 2 * s.C <= self.stats.numel(), (bnkey, nrows)
             coef = self._bn_coef_op(bnkey, self.stats, nrows)
-            ops += [lambda st, ctx: check(lib.gdrn_bn_bwd_reduce(ptr(dy), ptr(ym), ptr(raw), ptr(s.mean), ptr(s.invstd), ptr(msc), ptr(msh), s.npix,
-                                                                s.C, ptr(self.stats), e.dt, st), "bn_bwd_reduce"), coef]
+            ops += [_launch(lib.gdrn_bn_bwd_reduce, "bn_bwd_reduce", (dy, ym, raw, s.mean, s.invstd, msc, msh, s.npix, s.C, self.stats, e.dt)), coef]
         if xf:
             assert g_out is None and ym is None
             mode = 4 if msc is not None else 3
             return ops, dict(mode=mode, x2=raw, a=s.ka, b=s.kb, c=s.kc, msc=msc, msh=msh, out=dx, relu=False)
         if apply:
-            ops.append(lambda st, ctx: check(lib.gdrn_bn_bwd_apply(ptr(dy), ptr(ym), ptr(raw), ptr(s.ka), ptr(s.kb), ptr(s.kc), ptr(msc), ptr(msh), s.npix,
-                                                                   s.C, ptr(dx), ptr(g_out), e.dt, st), "bn_bwd_apply"))
+            ops.append(_launch(lib.gdrn_bn_bwd_apply, "bn_bwd_apply", (dy, ym, raw, s.ka, s.kb, s.kc, msc, msh, s.npix, s.C, dx, g_out, e.dt)))
         return ops
 
     def _unpack_task(self, L, packed_ptr, grad, rows_valid, rows_off=0):
@@ -585,94 +613,42 @@ class Plan:
         e = self.e
         op.bucket_end = True
         g = self.bwd_groups[e.bucket_first_group[bkt]]
-        if e.wgrad_stream and e.tail_overlap and bkt == len(e.bucket_first_group) - 1 and e.bucket_first_group[bkt] == 0:
-            n = getattr(self, "_front_n", 0)
-            g.insert(n, op)
-            self._front_n = n + 1
+        if e.wgrad_stream and bkt == len(e.bucket_first_group) - 1 and e.bucket_first_group[bkt] == 0:
+            g.insert(self._front_n, op)
+            self._front_n += 1
         else:
             g.append(op)
 
+    def _table_op(self, fn, what, tasks, starts, tables, *extra):
+        """side-stream launch fn(table of `tasks`, workgroup range starts, number of tasks, number of workgroups, *extra); `tables` keeps the
+        two device tensors"""
+        tab = cabi.to_device_table(tasks, self.e.dev)
+        stt = torch.tensor(starts, dtype=torch.int32, device=self.e.dev)
+        tables.append((tab, stt))
+        op = _launch(fn, what, (tab, stt, len(tasks), starts[-1]) + extra)
+        op.side = True
+        return op
+
     def _finish_unpack(self):
-        """One gdrn_unpack_multi per gradient bucket (pnp | head | layer4 | layer3 | rest), appended to the backward group that
-        completes the bucket, so the RCCL exchange of a bucket still starts as soon as its gradients exist."""
-        from .cabi import to_device_table
+        """The bucket-end work of every gradient bucket (pnp | head | layer4 | layer3 | rest): one grouped weight-gradient launch, one
+        gdrn_unpack_multi and one reduction of the weight-gradient partials, appended to the backward group that completes the bucket, so
+        the RCCL exchange of a bucket still starts as soon as its gradients exist."""
+        from .cabi import WreduceTask
 
         e, lib = self.e, self.e.lib
         chunk = lib.gdrn_pack_chunk()
-        ng = len(self.bwd_groups)
-        assert ng == 29, ng
+        assert len(self.bwd_groups) == 29, len(self.bwd_groups)
         # backward groups in forward order: stem(0) layer1(1-3) layer2(4-7) layer3(8-13) layer4(14-16) convT(17) head convs(18-23)
         # head out(24) pnp convs(25-27) fc(28)
         first_group = e.bucket_first_group  # forward index of the LAST-executed group of each bucket
-        from .cabi import WreduceTask
-
         bucket_of = lambda gi: next(i for i, g0 in enumerate(first_group) if gi >= g0)
-        # ---- grouped halo weight gradients: a common number of 8x8 pixel patches per workgroup within a bucket, chosen so
-        # that the bucket's grid has ~wgrad_blocks workgroups (2 per CU resident); longest-running tasks first
-        # launch groups = the buckets
-        cuts = sorted(set(first_group) | set(e.wgrad_cuts), reverse=True)
-        cut_of = lambda gi: next(c for c in cuts if gi >= c)
-        wg_bucket = {c: [] for c in cuts}
+        wg_bucket = {i: [] for i in range(len(first_group))}
         for gi, L, wp, fb in self._wgrad_deferred:
-            wg_bucket[cut_of(gi)].append((L, wp, fb))
+            wg_bucket[bucket_of(gi)].append((L, wp, fb))
         self._wgrad_tables = []
-        for cut, items_all in wg_bucket.items():
-            if not items_all:
-                continue
-            bkt = bucket_of(cut)
-            last_bucket = bkt == len(first_group) - 1
-            items, kind, cot, nblocks_target = items_all, 0, 64, e.wgrad_blocks   # one grouped launch of the 64 x 64 tile per bucket
-            # work of a layer in 32-pixel k-steps: an 8x8-pixel stage (stride 1) is two, a 4x8-pixel stage (stride 2) one
-            geo = []
-            for L, wp, flops in items:
-                s2 = wp.stride == 2
-                npatch = (wp.M // (wp.Ho * wp.Wo)) * (wp.Ho // (4 if s2 else 8)) * (wp.Wo // 8)
-                geo.append((npatch, npatch * (1 if s2 else 2), (wp.Cout // cot) * (wp.Cin // 64)))
-            # k-steps per workgroup: the grid's target, but no more than the layers of a shape class that carries >= 20 % of the bucket's work
-            # have -- a layer with fewer k-steps than `per` runs as ONE split of short workgroups beside the others' long ones (r6: layer4's 128
-            # against 171-256 for layer3 in their common launch: 434 us stand-alone against 322 with 128 everywhere, -0.06 ms per step;
-            # profiles/r06_wgrad_bucket_balance.txt).  Small classes (the head's ConvTranspose: 1 % of its bucket) do not set the length.
-            total = sum(u * t for _, u, t in geo)
-            share = {}
-            for _, u, t in geo:
-                share[u] = share.get(u, 0) + u * t
-            # (floor of 64 k-steps: only the Patch-PnP bucket sits on it -- 168 instead of 672 partial tiles for its reduction to read; r6: -0.02 ms)
-            per = max(64 if self.B >= 32 else 16, min([total // nblocks_target] + [u for u, w in share.items() if 5 * w >= total]))
-            tasks = []
-            for (L, wp, flops), (npatch, units, tiles) in zip(items, geo):
-                wp.variant = kind
-                wp.ws = ptr(e.dwp_flat)  # non-null placeholder for the split query
-                wp.splits = max(1, units // per)
-                wp.splits = int(lib.gdrn_conv3x3_wgrad_splits(C.byref(wp)))  # normalised: no empty split
-                assert wp.splits >= 1, (L.key, kind)
-                ws = e._empty(wp.splits * wp.Cout * wp.Cin * 9, dtype=torch.float32)
-                self.keep.append(ws)
-                wp.ws, wp.dw = ptr(ws), None
-                # the kernel's "Cin" role = the parameter's input channels for a conv (69 real of 128 for Patch-PnP's first conv), its
-                # second dimension for the ConvTranspose (weight [Cin_w][Cout_w][3][3] with x = output gradient, dy = input)
-                self._wreduce[L.key] = (ws, wp.splits, wp.Cout, wp.Cin, L.O if L.kind == "convT" else L.I)
-                tasks.append((-(units // wp.splits), len(tasks), wp, tiles, flops))
-            tasks.sort(key=lambda t: t[:2])
-            starts = [0]
-            for _, _, wp, tiles, _ in tasks:
-                starts.append(starts[-1] + tiles * wp.splits)
-            tab = to_device_table([t[2] for t in tasks], e.dev)
-            stt = torch.tensor(starts, dtype=torch.int32, device=e.dev)
-            self._wgrad_tables.append((tab, stt))
-            nt, nb = len(tasks), starts[-1]
-
-            def run(st, ctx, tab=tab, stt=stt, nt=nt, nb=nb, lds=(0 if last_bucket else e.wgrad_side_lds)):
-                # on the side stream (wgrad_stream) a bucket's weight gradients run under the NEXT bucket's data-gradient chain with one
-                # workgroup per CU (LDS request), so that the chain's workgroups find room on every CU; the last bucket has nothing to hide under
-                check(lib.gdrn_conv3x3_wgrad_multi_lds(ptr(tab), ptr(stt), nt, nb, lds if (e.wgrad_stream or e.wgrad_force_lds) else 0, st), "conv3x3_wgrad_multi")
-
-            run.meta = dict(kernel="conv3x3_wgrad_multi_kernel", flops=sum(t[4][0] for t in tasks), bytes=sum(t[4][1] for t in tasks),
-                            layer=f"bucket{bkt}@{cut}:wgrad x{nt} ({nb} wg)")
-            run.side = True
-            if cut in first_group:
-                self._bucket_end(bkt, run)
-            else:
-                self.bwd_groups[cut].append(run)   # behind the data gradients of group `cut`, the last-executed one of this launch
+        for bkt, items in wg_bucket.items():
+            if items:
+                self._bucket_end(bkt, self._grouped_wgrad(bkt, items))
 
         per_bucket = {i: [] for i in range(len(first_group))}
         red_bucket = {i: [] for i in range(len(first_group))}
@@ -696,73 +672,112 @@ class Plan:
             starts = [0]
             for t in tasks:
                 starts.append(starts[-1] + (cabi.transpose_blocks(lib, t) or (t.n + chunk - 1) // chunk))   # (fc1's gradient: 64 x 64 tiles through LDS)
-            tab = to_device_table(tasks, e.dev)
-            stt = torch.tensor(starts, dtype=torch.int32, device=e.dev)
-            self._unpack_tables.append((tab, stt))
-            nt, nb = len(tasks), starts[-1]
-            def unpack(st, ctx, tab=tab, stt=stt, nt=nt, nb=nb):
-                check(lib.gdrn_unpack_multi(ptr(tab), ptr(stt), nt, nb, st), "unpack_multi")
-
-            unpack.side = True
-            self._bucket_end(bkt, unpack)
+            self._bucket_end(bkt, self._table_op(lib.gdrn_unpack_multi, "unpack_multi", tasks, starts, self._unpack_tables))
         for bkt, tasks in red_bucket.items():
             if not tasks:
                 continue
             starts = [0]
             for t in tasks:
                 starts.append(starts[-1] + t.Cout * t.Cin // 256)
-            tab = to_device_table(tasks, e.dev)
-            stt = torch.tensor(starts, dtype=torch.int32, device=e.dev)
-            self._unpack_tables.append((tab, stt))
-            nt, nb = len(tasks), starts[-1]
-            def wreduce(st, ctx, tab=tab, stt=stt, nt=nt, nb=nb):
-                check(lib.gdrn_wgrad_reduce_multi(ptr(tab), ptr(stt), nt, nb, st), "wgrad_reduce_multi")
+            self._bucket_end(bkt, self._table_op(lib.gdrn_wgrad_reduce_multi, "wgrad_reduce_multi", tasks, starts, self._unpack_tables))
 
-            wreduce.side = True
-            self._bucket_end(bkt, wreduce)
+    def _grouped_wgrad(self, bkt, items):
+        """the halo weight gradients [(layer, WgradParams, (flops, bytes))] of gradient bucket bkt as ONE launch of the 64 x 64 tile: a common
+        number of 8x8 pixel patches per workgroup, chosen so that the grid has ~wgrad_blocks workgroups; longest-running tasks first"""
+        e, lib = self.e, self.e.lib
+        # work of a layer in 32-pixel k-steps: an 8x8-pixel stage (stride 1) is two, a 4x8-pixel stage (stride 2) one
+        geo = []
+        for L, wp, flops in items:
+            s2 = wp.stride == 2
+            npatch = (wp.M // (wp.Ho * wp.Wo)) * (wp.Ho // (4 if s2 else 8)) * (wp.Wo // 8)
+            geo.append((npatch, npatch * (1 if s2 else 2), (wp.Cout // 64) * (wp.Cin // 64)))
+        # k-steps per workgroup: the grid's target, but no more than the layers of a shape class that carries >= 20 % of the bucket's work
+        # have -- a layer with fewer k-steps than `per` runs as ONE split of short workgroups beside the others' long ones (r6: layer4's 128
+        # against 171-256 for layer3 in their common launch: 434 us stand-alone against 322 with 128 everywhere, -0.06 ms per step;
+        # profiles/r06_wgrad_bucket_balance.txt).  Small classes (the head's ConvTranspose: 1 % of its bucket) do not set the length.
+        total = sum(u * t for _, u, t in geo)
+        share = {}
+        for _, u, t in geo:
+            share[u] = share.get(u, 0) + u * t
+        # (floor of 64 k-steps: only the Patch-PnP bucket sits on it -- 168 instead of 672 partial tiles for its reduction to read; r6: -0.02 ms)
+        per = max(64 if self.B >= 32 else 16, min([total // e.wgrad_blocks] + [u for u, w in share.items() if 5 * w >= total]))
+        tasks = []
+        for (L, wp, flops), (npatch, units, tiles) in zip(items, geo):
+            wp.variant = 0
+            wp.ws = ptr(e.dwp_flat)  # non-null placeholder for the split query
+            wp.splits = max(1, units // per)
+            wp.splits = int(lib.gdrn_conv3x3_wgrad_splits(C.byref(wp)))  # normalised: no empty split
+            assert wp.splits >= 1, L.key
+            ws = e._empty(wp.splits * wp.Cout * wp.Cin * 9, dtype=torch.float32)
+            self.keep.append(ws)
+            wp.ws, wp.dw = ptr(ws), None
+            # the kernel's "Cin" role = the parameter's input channels for a conv (69 real of 128 for Patch-PnP's first conv), its
+            # second dimension for the ConvTranspose (weight [Cin_w][Cout_w][3][3] with x = output gradient, dy = input)
+            self._wreduce[L.key] = (ws, wp.splits, wp.Cout, wp.Cin, L.O if L.kind == "convT" else L.I)
+            tasks.append((-(units // wp.splits), len(tasks), wp, tiles, flops))
+        tasks.sort(key=lambda t: t[:2])
+        starts = [0]
+        for _, _, wp, tiles, _ in tasks:
+            starts.append(starts[-1] + tiles * wp.splits)
+        # on the side stream (wgrad_stream) a bucket's weight gradients run under the NEXT bucket's data-gradient chain with one
+        # workgroup per CU (LDS request), so that the chain's workgroups find room on every CU; the last bucket has nothing to hide under
+        last_bucket = bkt == len(e.bucket_first_group) - 1
+        lds = e.wgrad_side_lds if (not last_bucket and (e.wgrad_stream or e.wgrad_force_lds)) else 0
+        run = self._table_op(lib.gdrn_conv3x3_wgrad_multi_lds, "conv3x3_wgrad_multi", [t[2] for t in tasks], starts, self._wgrad_tables, lds)
+        run.meta = dict(kernel="conv3x3_wgrad_multi_kernel", flops=sum(t[4][0] for t in tasks), bytes=sum(t[4][1] for t in tasks),
+                        layer=f"bucket{bkt}@{e.bucket_first_group[bkt]}:wgrad x{len(tasks)} ({starts[-1]} wg)")
+        return run
 
     # ---- graph -------------------------------------------------------------------------------
     def _build(self):
+        """The graph in forward order.  Every stage builder appends its launches to self.fwd and, with a backward graph, ONE group to
+        self.bwd_groups; what a stage hands to the next travels in a cursor (NS) per chain:
+          backbone  x, d_x (block input and its gradient buffer), Hc, inpl, prev_raw2 (bn2 input of the previous block), pend
+          head      hx, d_hx, Hh, prev_bn, prev_raw, pend_h, up_next
+          Patch-PnP px, d_px, Hp, cin"""
         e, lib, B = self.e, self.e.lib, self.B
-        S, T, WL = self.bn_train, self.has_backward, self.with_loss  # batch stats | backward graph | losses
-        FOLD = (not S) and e.fold_bn  # eval mode: BatchNorm folded into the preceding conv (weights pre-scaled, shift as bias)
-
-        def E(*shape, dtype=None):
-            # every plan buffer is pinned in self.keep: the pre-bound C structs hold RAW device pointers, so a
-            # buffer referenced only through them would otherwise be returned to the caching allocator when
-            # _build() returns and be handed out again while the kernels still write to it
-            t = e._empty(*shape, dtype=dtype)
-            self.keep.append(t)
-            return t
-
-        F32t = torch.float32
         # per-tile BN partial sums, max over layers: conv tiles need <= B*32768 floats (64-pixel tiles of the 64x64 maps at 256
         # channels); the direct stem kernel writes one [2][64] row per wave
         n_stats = max(B * 32768 + 65536, 1024 * 2 * 512)  # ... and gdrn_bn_bwd_reduce writes <= 1024 rows of 2*C floats
         if e.stem_direct:
             n_stats = max(n_stats, int(lib.gdrn_stem_stats_rows(B)) * 128)
-        self.stats = E(n_stats, dtype=F32t)
-        self.stats_b = E(B * 4096 + 4096, dtype=F32t)   # rows of a fused 1x1 shortcut conv (gdrn_conv3x3s2: <= B * 16 tiles x 2 x 128 channels)
-        nreg = e.nreg
+        self.stats = self._E(n_stats, dtype=F32t)
+        self.stats_b = self._E(B * 4096 + 4096, dtype=F32t)   # rows of a fused 1x1 shortcut conv (gdrn_conv3x3s2: <= B * 16 tiles x 2 x 128 channels)
+        bb = self._stem()
+        for li, (nb, pl) in enumerate(zip(RESNET34_LAYERS, RESNET34_PLANES), start=1):
+            for b in range(nb):
+                self._block(bb, li, b, nb, pl)
+        assert bb.pend is None
+        hd = self._head_convT(bb.x, bb.d_x, bb.prev_raw2)
+        for hi in range(len(HEAD_CONVS)):
+            self._head_conv(hd, hi)
+        assert hd.pend_h is None
+        self._head_out(hd)
+        pn = NS(px=self.pnp_in, d_px=self.d_pnp_in if self.has_backward else None, Hp=64, cin=128)
+        for ci, gi in ((0, 1), (3, 4), (6, 7)):
+            self._pnp_conv(pn, ci, gi)
+        f1, f2 = self._fc_fwd(pn.px)
+        if self.has_backward:
+            self._fc_bwd(pn.px, pn.d_px, f1, f2)
+        self._pose()
 
-        # ---------------- stem
+    def _stem(self):
+        """image pack, conv1 7x7 stride 2, bn1, ReLU, max-pool (backward group 0).  Returns the backbone cursor."""
+        e, lib, B, S, E = self.e, self.e.lib, self.B, self.bn_train, self._E
         Ls = e.layers["backbone.conv1"]
         self.img_p = e._zeros(B, 262, 272, 4)
         fused_stem = e.stem_direct and not S   # eval mode: conv + bn1 + ReLU + max-pool in one kernel (gdrn_stem_conv_pool): no raw0 / idx0
         raw0 = None if fused_stem else E(B, 128, 128, 64)
         p0 = E(B, 64, 64, 64)
         idx0 = None if fused_stem else E(B, 64, 64, 64, dtype=torch.uint8)
+        flops = 2.0 * B * 128 * 128 * 64 * 147
         self.fwd.append(lambda st, ctx: check(lib.gdrn_pack_image(ctx["img"], ptr(self.img_p), B, 256, 256, 262, 272, e.dt, st), "pack_image"))
         if fused_stem:
             cp = None
         elif e.stem_direct:
             cp = NS(_stats_rows=int(lib.gdrn_stem_stats_rows(B)))
-
-            def stem(st, ctx):
-                check(lib.gdrn_stem_conv(ptr(self.img_p), ptr(e.stem_w32), ptr(raw0), ptr(self.stats) if S else None, B, e.dt, st), "stem_conv")
-
-            stem.meta = dict(kernel="stem_conv_kernel", flops=2.0 * B * 128 * 128 * 64 * 147, layer="backbone.conv1")
-            self.fwd.append(stem)
+            self.fwd.append(_launch(lib.gdrn_stem_conv, "stem_conv", (self.img_p, e.stem_w32, raw0, self.stats if S else None, B, e.dt),
+                                    dict(kernel="stem_conv_kernel", flops=flops, layer="backbone.conv1")))
         else:
             op, cp = self._conv(Ls, self.img_p, 4, raw0, 262, 272, 128, 128, 2, 0, cin=64, cout=64, x_cs=4, KH=7, KW=1,
                                 stats=self.stats if S else None)
@@ -770,235 +785,228 @@ class Plan:
         self.fwd += self._bn_fwd("backbone.bn1", raw0, cp, 64, B * 128 * 128, None)
         s0 = self.bn["backbone.bn1"]
         if fused_stem:
-            def stem_pool(st, ctx):
-                check(lib.gdrn_stem_conv_pool(ptr(self.img_p), ptr(e.stem_w32), ptr(s0.scale), ptr(s0.shift), ptr(p0), B, e.dt, st), "stem_conv_pool")
-
-            stem_pool.meta = dict(kernel="stem_conv_pool_kernel", flops=2.0 * B * 128 * 128 * 64 * 147, layer="backbone.conv1+bn1+relu+maxpool")
-            self.fwd.append(stem_pool)
+            self.fwd.append(_launch(lib.gdrn_stem_conv_pool, "stem_conv_pool", (self.img_p, e.stem_w32, s0.scale, s0.shift, p0, B, e.dt),
+                                    dict(kernel="stem_conv_pool_kernel", flops=flops, layer="backbone.conv1+bn1+relu+maxpool")))
         else:
-            self.fwd.append(lambda st, ctx: check(lib.gdrn_bn_relu_maxpool_fwd(ptr(raw0), ptr(s0.scale), ptr(s0.shift), ptr(p0), ptr(idx0),
-                                                                               B, 128, 128, 64, e.dt, st), "bn_relu_maxpool"))
+            self.fwd.append(_launch(lib.gdrn_bn_relu_maxpool_fwd, "bn_relu_maxpool", (raw0, s0.scale, s0.shift, p0, idx0, B, 128, 128, 64, e.dt)))
         self.tensors.update({"stem.pool": p0} if fused_stem else {"stem.raw": raw0, "stem.pool": p0})
-        if T:
-            d_p0 = E(B, 64, 64, 64)
-            g_stem = E(B, 128, 128, 64)
-            d_raw0 = g_stem  # in place
-            self.tensors.update({"stem.d_pool": d_p0, "stem.g": g_stem})
-            # with the fused stem weight gradient the max-pool backward also emits the BatchNorm-backward sums of the gradient it
-            # writes (one partial row per workgroup): no separate reduce pass over the two 134 MB tensors
-            mp_rows = int(lib.gdrn_maxpool_bwd_rows(B, 128, 128, 64, e.dt)) if e.stem_wgrad else 0
+        if not self.has_backward:
+            return NS(x=p0, d_x=None, Hc=64, inpl=64, prev_raw2=None, pend=None)
+        d_p0 = E(B, 64, 64, 64)
+        g_stem = E(B, 128, 128, 64)
+        self.tensors.update({"stem.d_pool": d_p0, "stem.g": g_stem})
+        if e.stem_direct:
+            # the max-pool backward also emits the BatchNorm-backward sums of the gradient it writes (one partial row per workgroup): no
+            # separate reduce pass over the two 134 MB tensors.  The stem has no data gradient: its BatchNorm-backward apply is evaluated
+            # inside the weight-gradient kernel while the dy tile is staged (no 134 MB d_raw0 round trip, dy read once instead of once per
+            # kernel row)
+            mp_rows = int(lib.gdrn_maxpool_bwd_rows(B, 128, 128, 64, e.dt))
             assert mp_rows * 2 * 64 <= self.stats.numel()
-            grp = [lambda st, ctx: check(lib.gdrn_maxpool_bwd(ptr(d_p0), ptr(idx0), ptr(raw0), ptr(s0.scale), ptr(s0.shift),
-                                                              ptr(g_stem), B, 128, 128, 64, ptr(s0.mean) if mp_rows else None,
-                                                              ptr(s0.invstd) if mp_rows else None, ptr(self.stats) if mp_rows else None, e.dt, st),
-                                         "maxpool_bwd")]
-            if e.stem_wgrad:
-                # the stem has no data gradient: its BatchNorm-backward apply is evaluated inside the weight-gradient kernel while
-                # the dy tile is staged (no 134 MB d_raw0 round trip, dy read once instead of once per kernel row)
-                sb = self.bn["backbone.bn1"]
-                gam, dgam, dbet = e.P["backbone.bn1.weight"], e.grads["backbone.bn1.weight"], e.grads["backbone.bn1.bias"]
-                gw = e.grads["backbone.conv1.weight"]
-                assert gw.is_contiguous() and gw.dtype == torch.float32
-                sw_ws = e._empty(int(lib.gdrn_stem_wgrad_parts(B)) * 64 * 224, dtype=torch.float32)
-                grp.append(self._bn_coef_op("backbone.bn1", self.stats, mp_rows))  # rows -> (a, b, c), dgamma, dbeta; the apply is fused below
-
-                def stem_wgrad(st, ctx, a=(self.img_p, g_stem, raw0, sb.ka, sb.kb, sb.kc, sw_ws, gw)):
-                    # tensors bound as a default argument: _build() reuses short local names further down (late-binding closures)
-                    check(lib.gdrn_stem_wgrad(ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3]), ptr(a[4]), ptr(a[5]), B, ptr(a[6]), ptr(a[7]), e.dt | PREZEROED, st),
-                          "stem_wgrad")
-
-                self._zero_regions.append(self._grad16(gw))
-
-                self.grad_group["backbone.conv1.weight"] = len(self.bwd_groups)
-                stem_wgrad.meta = dict(kernel="stem_wgrad_kernel", flops=2.0 * B * 128 * 128 * 64 * 147, layer="backbone.conv1:wgrad")
-                grp.append(stem_wgrad)
-            else:
-                grp += self._bn_bwd("backbone.bn1", g_stem, None, raw0, d_raw0)
-                grp.append(self._wgrad(Ls, self.img_p, d_raw0, 262, 272, 128, 128, 2, 0, 64, 64, 4, 64, KH=7, KW=1))
-                grp.append(self._unpack(Ls))
-            self.bwd_groups.append(grp)
+            grp = [_launch(lib.gdrn_maxpool_bwd, "maxpool_bwd", (d_p0, idx0, raw0, s0.scale, s0.shift, g_stem, B, 128, 128, 64, s0.mean if mp_rows else None,
+                                                                s0.invstd if mp_rows else None, self.stats if mp_rows else None, e.dt))]
+            gw = e.grads["backbone.conv1.weight"]
+            assert gw.is_contiguous() and gw.dtype == torch.float32
+            sw_ws = e._empty(int(lib.gdrn_stem_wgrad_parts(B)) * 64 * 224, dtype=torch.float32)
+            grp.append(self._bn_coef_op("backbone.bn1", self.stats, mp_rows))  # rows -> (a, b, c), dgamma, dbeta; the apply is fused below
+            self._zero_regions.append(self._grad16(gw))
+            self.grad_group["backbone.conv1.weight"] = len(self.bwd_groups)
+            grp.append(_launch(lib.gdrn_stem_wgrad, "stem_wgrad", (self.img_p, g_stem, raw0, s0.ka, s0.kb, s0.kc, B, sw_ws, gw, e.dt | PREZEROED),
+                               dict(kernel="stem_wgrad_kernel", flops=flops, layer="backbone.conv1:wgrad")))
         else:
-            d_p0 = None
+            grp = [_launch(lib.gdrn_maxpool_bwd, "maxpool_bwd", (d_p0, idx0, raw0, s0.scale, s0.shift, g_stem, B, 128, 128, 64, None, None, None, e.dt))]
+            grp += self._bn_bwd("backbone.bn1", g_stem, None, raw0, g_stem)   # (in place)
+            grp.append(self._wgrad(Ls, self.img_p, g_stem, 262, 272, 128, 128, 2, 0, 64, 64, 4, 64, KH=7, KW=1))
+            grp.append(self._unpack(Ls))
+        self.bwd_groups.append(grp)
+        return NS(x=p0, d_x=d_p0, Hc=64, inpl=64, prev_raw2=None, pend=None)
 
-        # ---------------- residual blocks
-        # `pend`: the block input `x` is not materialised yet -- it is v = relu(a*x1 + b*x2 + c) of the previous block's bn2 output
-        # and identity, evaluated (and written to `x`) by THIS block's conv1 while it stages its patch (xf, see _conv)
-        x, d_x, Hc, inpl = p0, d_p0, 64, 64
+    def _block(self, c, li, b, nb, pl):
+        """BasicBlock b of layer li (nb blocks, pl planes) behind the backbone cursor c, which it advances.
+        c.pend: the block input c.x is not materialised yet -- it is v = relu(a*x1 + b*x2 + c) of the previous block's bn2 output and
+        identity, evaluated (and written to c.x) by THIS block's conv1 while it stages its patch (xf, see _conv)"""
+        e, B, E = self.e, self.B, self._E
+        pfx = f"backbone.layer{li}.{b}"
+        stride = 2 if (b == 0 and li > 1) else 1
+        Ho = c.Hc // stride
+        k = NS(pfx=pfx, li=li, b=b, nb=nb, pl=pl, stride=stride, Ho=Ho, L1=e.layers[pfx + ".conv1"], L2=e.layers[pfx + ".conv2"],
+               Ld=e.layers.get(pfx + ".downsample.0"), rawd=None)
+        k.raw1, k.a1, k.raw2, k.out = E(B, Ho, Ho, pl), E(B, Ho, Ho, pl), E(B, Ho, Ho, pl), E(B, Ho, Ho, pl)
+        self.tensors.update({pfx + ".raw1": k.raw1, pfx + ".a1": k.a1, pfx + ".raw2": k.raw2, pfx + ".out": k.out})
         pend = None
-        for li, (nb, pl) in enumerate(zip(RESNET34_LAYERS, RESNET34_PLANES), start=1):
-            for b in range(nb):
-                pfx = f"backbone.layer{li}.{b}"
-                stride = 2 if (b == 0 and li > 1) else 1
-                Ho = Hc // stride
-                L1, L2 = e.layers[pfx + ".conv1"], e.layers[pfx + ".conv2"]
-                Ld = e.layers.get(pfx + ".downsample.0")
-                npo = B * Ho * Ho
-                raw1, a1, raw2, out = E(B, Ho, Ho, pl), E(B, Ho, Ho, pl), E(B, Ho, Ho, pl), E(B, Ho, Ho, pl)
-                self.tensors.update({pfx + ".raw1": raw1, pfx + ".a1": a1, pfx + ".raw2": raw2, pfx + ".out": out})
-                if FOLD and e.block64 and Ld is None and inpl == 64 and pl == 64 and e.use_halo and B >= e.halo_min_b and L1.wfF is not None \
-                        and L1.wfmt.get("e", 1) == 1 and L2.wfmt.get("e", 1) == 1 and int(lib.gdrn_block64_eval_ok(B, Hc, Hc, e.dt)):
-                    # eval, 64 channels (layer1): the whole BasicBlock as ONE launch, the intermediate in LDS (r6, csrc/block64.hip)
-                    f1, f2 = e.fold(pfx + ".bn1", L1), e.fold(pfx + ".bn2", L2)
-                    L1.wfmt["e"] = L2.wfmt["e"] = 1   # (fragment-major layout of the first halo kernel: what gdrn_block64_eval reads)
-                    if not self._fold_hooked:
-                        self.eval_prep.append(lambda st, ctx: self.e.eval_refresh())
-                        self._fold_hooked = True
+        if not self.bn_train:
+            self._block_eval(c, k)
+        else:
+            pend = self._block_fwd(c, k)
+            if self.has_backward:
+                self._block_bwd(c, k)
+        c.x, c.Hc, c.inpl, c.prev_raw2, c.pend = k.out, Ho, pl, k.raw2, pend
 
-                    def blk(st, ctx, x=x, out=out, L1=L1, L2=L2, f1=f1, f2=f2, Hc=Hc):
-                        check(lib.gdrn_block64_eval(ptr(x), ptr(L1.wfF_e), ptr(f1.shift), ptr(L2.wfF_e), ptr(f2.shift), ptr(out), B, Hc, Hc, e.dt, st), "block64_eval")
+    def _block_eval(self, c, k):
+        """eval mode: BatchNorm folded into the preceding conv (weights pre-scaled, shift as bias) -- one launch for a 64-channel block,
+        three (four) otherwise, no BatchNorm passes"""
+        e, lib, B = self.e, self.e.lib, self.B
+        x, Hc, inpl = c.x, c.Hc, c.inpl
+        pfx, pl, Ho, stride, L1, L2, Ld, a1, out = k.pfx, k.pl, k.Ho, k.stride, k.L1, k.L2, k.Ld, k.a1, k.out
+        if e.block64 and Ld is None and inpl == 64 and pl == 64 and e.use_halo and B >= e.halo_min_b and L1.wfF is not None \
+                and L1.wfmt.get("e", 1) == 1 and L2.wfmt.get("e", 1) == 1 and int(lib.gdrn_block64_eval_ok(B, Hc, Hc, e.dt)):
+            # 64 channels (layer1): the whole BasicBlock as ONE launch, the intermediate in LDS (r6, csrc/block64.hip)
+            f1, f2 = e.fold(pfx + ".bn1", L1), e.fold(pfx + ".bn2", L2)
+            L1.wfmt["e"] = L2.wfmt["e"] = 1   # (fragment-major layout of the first halo kernel: what gdrn_block64_eval reads)
+            self._hook_fold()
+            self.fwd.append(_launch(lib.gdrn_block64_eval, "block64_eval", (x, L1.wfF_e, f1.shift, L2.wfF_e, f2.shift, out, B, Hc, Hc, e.dt),
+                                    dict(kernel="block64_eval_kernel", flops=2.0 * 2 * B * Hc * Hc * 64 * 64 * 9, layer=pfx + ".conv1+conv2")))
+            del self.tensors[pfx + ".raw1"], self.tensors[pfx + ".a1"], self.tensors[pfx + ".raw2"]
+            return
+        s2op = None
+        if Ld is not None and e.s2_halo and L1.wfF is not None:
+            # stage entry: conv1 (3x3 stride 2) and the 1x1 shortcut in ONE launch of the parity-plane kernel (r6), BatchNorms folded
+            f1, fd = e.fold(pfx + ".bn1", L1), e.fold(pfx + ".downsample.1", Ld)
+            self._hook_fold()
+            res = self._E(B, Ho, Ho, pl)
+            s2op = self._s2(L1, x, inpl, a1, Hc, Ho, Ld=Ld, yd=res, bias=f1.shift, bias_d=fd.shift, act=1, evalw=True)
+        if s2op is not None:
+            self.fwd.append(s2op[0])
+        else:
+            self.fwd.append(self._conv_bn_eval(L1, pfx + ".bn1", x, inpl, a1, Hc, Hc, Ho, Ho, stride, 1, relu=True))
+        res = x if Ld is None else (res if s2op is not None else None)
+        if Ld is not None and s2op is None:
+            res = self._E(B, Ho, Ho, pl)
+            self.fwd.append(self._conv_bn_eval(Ld, pfx + ".downsample.1", x, inpl, res, Hc, Hc, Ho, Ho, stride, 0, relu=False))
+        self.fwd.append(self._conv_bn_eval(L2, pfx + ".bn2", a1, pl, out, Ho, Ho, Ho, Ho, 1, 1, relu=True, residual=res, add_cs=pl))
 
-                    blk.meta = dict(kernel="block64_eval_kernel", flops=2.0 * 2 * B * Hc * Hc * 64 * 64 * 9, layer=pfx + ".conv1+conv2")
-                    self.fwd.append(blk)
-                    del self.tensors[pfx + ".raw1"], self.tensors[pfx + ".a1"], self.tensors[pfx + ".raw2"]
-                    x, Hc, inpl, prev_raw2 = out, Ho, pl, raw2
-                    continue
-                if FOLD:  # eval: three (four) launches per block, no BatchNorm passes
-                    s2op = None
-                    if Ld is not None and e.s2_halo and L1.wfF is not None:
-                        # stage entry: conv1 (3x3 stride 2) and the 1x1 shortcut in ONE launch of the parity-plane kernel (r6), BatchNorms folded
-                        f1, fd = e.fold(pfx + ".bn1", L1), e.fold(pfx + ".downsample.1", Ld)
-                        if not self._fold_hooked:
-                            self.eval_prep.append(lambda st, ctx: self.e.eval_refresh())
-                            self._fold_hooked = True
-                        res = E(B, Ho, Ho, pl)
-                        s2op = self._s2(L1, x, inpl, a1, Hc, Ho, Ld=Ld, yd=res, bias=f1.shift, bias_d=fd.shift, act=1, evalw=True)
-                    if s2op is not None:
-                        self.fwd.append(s2op[0])
-                    else:
-                        self.fwd.append(self._conv_bn_eval(L1, pfx + ".bn1", x, inpl, a1, Hc, Hc, Ho, Ho, stride, 1, relu=True))
-                    res = x if Ld is None else (res if s2op is not None else None)
-                    if Ld is not None and s2op is None:
-                        res = E(B, Ho, Ho, pl)
-                        self.fwd.append(self._conv_bn_eval(Ld, pfx + ".downsample.1", x, inpl, res, Hc, Hc, Ho, Ho, stride, 0, relu=False))
-                    self.fwd.append(self._conv_bn_eval(L2, pfx + ".bn2", a1, pl, out, Ho, Ho, Ho, Ho, 1, 1, relu=True, residual=res, add_cs=pl))
-                    x, Hc, inpl, prev_raw2 = out, Ho, pl, raw2
-                    continue
-                assert pend is None or self._xf_ok(L1)
-                s2op = None
-                if Ld is not None and pend is None:
-                    # stage entry (r6): conv1 (3x3 stride 2) and the 1x1 shortcut conv in ONE launch of the parity-plane kernel, each with its
-                    # own BatchNorm-statistics rows
-                    rawd_ = E(B, Ho, Ho, pl)
-                    s2op = self._s2(L1, x, inpl, raw1, Hc, Ho, Ld=Ld, yd=rawd_, stats=self.stats if S else None, stats_d=self.stats_b if S else None)
-                if s2op is not None:
-                    op, cp, cpd_s2 = s2op
-                else:
-                    op, cp = self._conv(L1, pend["x1"] if pend else x, inpl, raw1, Hc, Hc, Ho, Ho, stride, 1, stats=self.stats if S else None,
-                                        xf=dict(pend["xf"], out=x) if pend else None)
-                self.fwd.append(op)
-                xf1 = self._xf_ok(L2, 1, Ho)  # bn1 + ReLU applied by conv2 on load (which also writes a1 for the weight gradient)
-                self.fwd += self._bn_fwd(pfx + ".bn1", raw1, cp, pl, npo, None if xf1 else a1)
-                s1 = self.bn[pfx + ".bn1"]
-                op, cp = self._conv(L2, raw1 if xf1 else a1, pl, raw2, Ho, Ho, Ho, Ho, 1, 1, stats=self.stats if S else None,
-                                    xf=dict(mode=1, a=s1.scale, c=s1.shift, relu=True, out=a1) if xf1 else None)
-                self.fwd.append(op)
-                # block output relu(bn2(raw2) + identity): left to the next block's conv1 when that is a halo launch
-                nxt1 = e.layers.get(f"backbone.layer{li}.{b + 1}.conv1")
-                xf_out = nxt1 is not None and self._xf_ok(nxt1, 2, Ho)
-                if Ld is not None:
-                    rawd, idn = (rawd_ if s2op is not None else E(B, Ho, Ho, pl)), (None if xf_out else E(B, Ho, Ho, pl))
-                    self.tensors[pfx + ".rawd"] = rawd
-                    if idn is not None:
-                        self.tensors[pfx + ".idn"] = idn
-                    self.fwd += self._bn_fwd(pfx + ".bn2", raw2, cp, pl, npo, None)
-                    if s2op is not None:   # (the shortcut conv ran with conv1: only its BatchNorm's finalize is left, from its own rows)
-                        self.fwd += self._bn_fwd(pfx + ".downsample.1", rawd, cpd_s2, pl, npo, idn, relu=0, stats=self.stats_b)
-                    else:
-                        op, cpd = self._conv(Ld, x, inpl, rawd, Hc, Hc, Ho, Ho, stride, 0, stats=self.stats if S else None)
-                        self.fwd.append(op)
-                        self.fwd += self._bn_fwd(pfx + ".downsample.1", rawd, cpd, pl, npo, idn, relu=0)
-                    s2, sd = self.bn[pfx + ".bn2"], self.bn[pfx + ".downsample.1"]
-                    if xf_out:   # relu(scale2*raw2 + scale_d*rawd + shift2 + shift_d)
-                        nxt_pend = dict(x1=raw2, xf=dict(mode=2, x2=rawd, a=s2.scale, b=sd.scale, c=s2.shift, c2=sd.shift, relu=True))
-                    else:
-                        self.fwd.append(lambda st, ctx, raw2=raw2, s2=s2, idn=idn, out=out, npo=npo, pl=pl: check(
-                            lib.gdrn_bn_apply(ptr(raw2), ptr(s2.scale), ptr(s2.shift), ptr(idn), ptr(out), npo, pl, 1, e.dt, st), "bn_apply"))
-                else:
-                    self.fwd += self._bn_fwd(pfx + ".bn2", raw2, cp, pl, npo, None if xf_out else out, residual=x)
-                    s2 = self.bn[pfx + ".bn2"]
-                    if xf_out:   # relu(scale2*raw2 + x + shift2)
-                        nxt_pend = dict(x1=raw2, xf=dict(mode=2, x2=x, a=s2.scale, c=s2.shift, relu=True))
-                if not xf_out:
-                    nxt_pend = None
-                if T:
-                    d_out = E(B, Ho, Ho, pl)
-                    d_raw2, d_a1, d_raw1 = E(B, Ho, Ho, pl), E(B, Ho, Ho, pl), E(B, Ho, Ho, pl)
-                    self.tensors.update({pfx + ".d_out": d_out, pfx + ".d_raw2": d_raw2, pfx + ".d_a1": d_a1, pfx + ".d_raw1": d_raw1})
-                    # d_out comes from the next block's conv1 data gradient when that is a plain (stride-1) block of the
-                    # same layer: its halo epilogue has then already applied this block's output ReLU mask and reduced
-                    # the bn2-backward sums (and d_out itself is the residual-path gradient g2)
-                    # ... or, for the last block of a layer, the generic kernel's epilogue (next layer's stride-2 conv1 / the head's ConvTranspose)
-                    pre2 = self._fusable(e.layers[f"backbone.layer{li}.{b + 1}.conv1"]) if b + 1 < nb else e.gemm_bnb
-                    # BatchNorm-backward apply passes fused into the data-gradient conv that consumes their result (xf modes 3 / 4)
-                    xfb2 = pre2 and self._xf_ok(L2, 3, Ho)
-                    need_dx = d_x is not None
-                    xfb1 = self._fusable(L2) and self._xf_ok(L1, 3, Ho) and Ld is None and need_dx
-                    xd2 = xd1 = None
-                    if xfb2:
-                        g2 = d_out
-                        grp, xd2 = self._bn_bwd(pfx + ".bn2", d_out, None, raw2, d_raw2, prereduced=True, xf=True)
-                    elif pre2:
-                        g2 = d_out
-                        grp = self._bn_bwd(pfx + ".bn2", d_out, None, raw2, d_raw2, prereduced=True)
-                    else:
-                        g2 = E(B, Ho, Ho, pl)
-                        self.tensors[pfx + ".g2"] = g2
-                        grp = self._bn_bwd(pfx + ".bn2", d_out, out, raw2, d_raw2, g_out=g2)
-                    grp.append(self._wgrad(L2, a1, d_raw2, Ho, Ho, Ho, Ho, 1, 1, pl, pl, pl, pl))
-                    grp.append(self._unpack(L2))
-                    pre1 = self._fusable(L2)
-                    op, _ = self._conv(L2, d_out if xfb2 else d_raw2, pl, d_a1, Ho, Ho, Ho, Ho, 1, 1, w=L2.wd, rows=L2.rows_d, cin=L2.cin_d, cout=pl,
-                                       bnb=(pfx + ".bn1", raw1, None, True) if pre1 else None, xf=xd2)
-                    grp.append(op)
-                    if xfb1:
-                        ops1, xd1 = self._bn_bwd(pfx + ".bn1", d_a1, a1, raw1, d_raw1, affine_mask=True, prereduced=True, xf=True)
-                        grp += ops1
-                    else:
-                        grp += self._bn_bwd(pfx + ".bn1", d_a1, a1, raw1, d_raw1, affine_mask=True, prereduced=pre1)
-                    grp.append(self._wgrad(L1, x, d_raw1, Hc, Hc, Ho, Ho, stride, 1, inpl, pl, inpl, pl))
-                    grp.append(self._unpack(L1))
-                    if Ld is not None:
-                        d_rawd, d_xd = E(B, Ho, Ho, pl), E(B, Hc, Hc, inpl)
-                        self.tensors.update({pfx + ".d_rawd": d_rawd, pfx + ".d_xd": d_xd})
-                        grp += self._bn_bwd(pfx + ".downsample.1", g2, None, rawd, d_rawd)
-                        grp.append(self._wgrad(Ld, x, d_rawd, Hc, Hc, Ho, Ho, stride, 0, inpl, pl, inpl, pl, defer=li >= 3))
-                        grp.append(self._unpack(Ld))
-                        pbn = f"backbone.layer{li - 1}.{RESNET34_LAYERS[li - 2] - 1}.bn2"
-                        # (r6) conv1's data gradient, the shortcut conv's data gradient and the previous block's ReLU mask + bn2-backward sums as
-                        # ONE launch of the parity-class kernel: no d_xd tensor (three quarters zeros), no addend pass
-                        s2d = self._s2d(L1, d_raw1, d_x, Ho, Hc, inpl, Ld=Ld, dyd=d_rawd, bnb=(pbn, prev_raw2, x)) if e.gemm_bnb else None
-                        if s2d is not None:
-                            grp.append(s2d)
-                            del self.tensors[pfx + ".d_xd"]
-                        else:
-                            op, _ = self._conv(Ld, d_rawd, pl, d_xd, Ho, Ho, Hc, Hc, 2, 0, mode=1, w=Ld.wd, rows=Ld.rows_d, cin=Ld.cin_d, cout=inpl)
-                            grp.append(op)
-                            # d_x = gradient w.r.t. the previous layer's last block output (mask = x): its bn2 backward is reduced here
-                            op, _ = self._conv(L1, d_raw1, pl, d_x, Ho, Ho, Hc, Hc, 2, 1, mode=1, w=L1.wd, rows=L1.rows_d, cin=L1.cin_d,
-                                               cout=inpl, addend=d_xd, add_cs=inpl, bnb=(pbn, prev_raw2, x, False) if e.gemm_bnb else None)
-                            grp.append(op)
-                    elif need_dx:
-                        # previous block of the same layer: d_x is the gradient w.r.t. its output (mask = x, stored) and
-                        # feeds its bn2 backward (raw input prev_raw2)
-                        fuse_prev = b >= 1 and self._fusable(L1)
-                        op, _ = self._conv(L1, d_a1 if xfb1 else d_raw1, pl, d_x, Ho, Ho, Hc, Hc, 1, 1, w=L1.wd, rows=L1.rows_d, cin=L1.cin_d, cout=inpl,
-                                           addend=g2, add_cs=pl,
-                                           bnb=(f"backbone.layer{li}.{b - 1}.bn2", prev_raw2, x, False) if fuse_prev else None, xf=xd1)
-                        grp.append(op)
-                    self.bwd_groups.append(grp)
-                    d_x = d_out
-                x, Hc, inpl, prev_raw2, pend = out, Ho, pl, raw2, nxt_pend
-        assert pend is None
-        feat, d_feat = x, d_x
+    def _block_fwd(self, c, k):
+        """training forward of a BasicBlock (batch statistics).  Sets k.rawd (shortcut conv output) and returns the next block's `pend`."""
+        e, B, S, E = self.e, self.B, self.bn_train, self._E
+        x, Hc, inpl, pend = c.x, c.Hc, c.inpl, c.pend
+        pfx, pl, Ho, stride, L1, L2, Ld, raw1, a1, raw2, out = k.pfx, k.pl, k.Ho, k.stride, k.L1, k.L2, k.Ld, k.raw1, k.a1, k.raw2, k.out
+        npo = B * Ho * Ho
+        assert pend is None or self._xf_ok(L1)
+        s2op = None
+        if Ld is not None and pend is None:
+            # stage entry (r6): conv1 (3x3 stride 2) and the 1x1 shortcut conv in ONE launch of the parity-plane kernel, each with its
+            # own BatchNorm-statistics rows
+            rawd_ = E(B, Ho, Ho, pl)
+            s2op = self._s2(L1, x, inpl, raw1, Hc, Ho, Ld=Ld, yd=rawd_, stats=self.stats if S else None, stats_d=self.stats_b if S else None)
+        if s2op is not None:
+            op, cp, cpd_s2 = s2op
+        else:
+            op, cp = self._conv(L1, pend["x1"] if pend else x, inpl, raw1, Hc, Hc, Ho, Ho, stride, 1, stats=self.stats if S else None,
+                                xf=dict(pend["xf"], out=x) if pend else None)
+        self.fwd.append(op)
+        xf1 = self._xf_ok(L2)  # bn1 + ReLU applied by conv2 on load (which also writes a1 for the weight gradient)
+        self.fwd += self._bn_fwd(pfx + ".bn1", raw1, cp, pl, npo, None if xf1 else a1)
+        s1 = self.bn[pfx + ".bn1"]
+        op, cp = self._conv(L2, raw1 if xf1 else a1, pl, raw2, Ho, Ho, Ho, Ho, 1, 1, stats=self.stats if S else None,
+                            xf=dict(mode=1, a=s1.scale, c=s1.shift, relu=True, out=a1) if xf1 else None)
+        self.fwd.append(op)
+        # block output relu(bn2(raw2) + identity): left to the next block's conv1 when that is a halo launch
+        nxt1 = e.layers.get(f"backbone.layer{k.li}.{k.b + 1}.conv1")
+        xf_out = nxt1 is not None and self._xf_ok(nxt1)
+        if Ld is None:
+            self.fwd += self._bn_fwd(pfx + ".bn2", raw2, cp, pl, npo, None if xf_out else out, residual=x)
+            s2 = self.bn[pfx + ".bn2"]
+            # relu(scale2*raw2 + x + shift2)
+            return dict(x1=raw2, xf=dict(mode=2, x2=x, a=s2.scale, c=s2.shift, relu=True)) if xf_out else None
+        k.rawd, idn = (rawd_ if s2op is not None else E(B, Ho, Ho, pl)), (None if xf_out else E(B, Ho, Ho, pl))
+        self.tensors[pfx + ".rawd"] = k.rawd
+        if idn is not None:
+            self.tensors[pfx + ".idn"] = idn
+        self.fwd += self._bn_fwd(pfx + ".bn2", raw2, cp, pl, npo, None)
+        if s2op is not None:   # (the shortcut conv ran with conv1: only its BatchNorm's finalize is left, from its own rows)
+            self.fwd += self._bn_fwd(pfx + ".downsample.1", k.rawd, cpd_s2, pl, npo, idn, relu=0, stats=self.stats_b)
+        else:
+            op, cpd = self._conv(Ld, x, inpl, k.rawd, Hc, Hc, Ho, Ho, stride, 0, stats=self.stats if S else None)
+            self.fwd.append(op)
+            self.fwd += self._bn_fwd(pfx + ".downsample.1", k.rawd, cpd, pl, npo, idn, relu=0)
+        s2, sd = self.bn[pfx + ".bn2"], self.bn[pfx + ".downsample.1"]
+        if xf_out:   # relu(scale2*raw2 + scale_d*rawd + shift2 + shift_d)
+            return dict(x1=raw2, xf=dict(mode=2, x2=k.rawd, a=s2.scale, b=sd.scale, c=s2.shift, c2=sd.shift, relu=True))
+        self.fwd.append(_launch(e.lib.gdrn_bn_apply, "bn_apply", (raw2, s2.scale, s2.shift, idn, out, npo, pl, 1, e.dt)))
+        return None
 
-        # ---------------- geometric head
+    def _block_bwd(self, c, k):
+        """backward group of a BasicBlock: bn2, conv2, bn1, conv1 (+ shortcut) -- writes c.d_x and moves it to this block's d_out"""
+        e, B, E = self.e, self.B, self._E
+        x, d_x, Hc, inpl, prev_raw2 = c.x, c.d_x, c.Hc, c.inpl, c.prev_raw2
+        pfx, li, b, pl, Ho, stride, L1, L2, Ld = k.pfx, k.li, k.b, k.pl, k.Ho, k.stride, k.L1, k.L2, k.Ld
+        raw1, a1, raw2, out, rawd = k.raw1, k.a1, k.raw2, k.out, k.rawd
+        d_out = E(B, Ho, Ho, pl)
+        d_raw2, d_a1, d_raw1 = E(B, Ho, Ho, pl), E(B, Ho, Ho, pl), E(B, Ho, Ho, pl)
+        self.tensors.update({pfx + ".d_out": d_out, pfx + ".d_raw2": d_raw2, pfx + ".d_a1": d_a1, pfx + ".d_raw1": d_raw1})
+        # d_out comes from the next block's conv1 data gradient when that is a plain (stride-1) block of the
+        # same layer: its halo epilogue has then already applied this block's output ReLU mask and reduced
+        # the bn2-backward sums (and d_out itself is the residual-path gradient g2)
+        # ... or, for the last block of a layer, the generic kernel's epilogue (next layer's stride-2 conv1 / the head's ConvTranspose)
+        pre2 = self._fusable(e.layers[f"backbone.layer{li}.{b + 1}.conv1"]) if b + 1 < k.nb else e.gemm_bnb
+        # BatchNorm-backward apply passes fused into the data-gradient conv that consumes their result (xf modes 3 / 4)
+        xfb2 = pre2 and self._xf_ok(L2)
+        need_dx = d_x is not None
+        xfb1 = self._fusable(L2) and self._xf_ok(L1) and Ld is None and need_dx
+        xd2 = xd1 = None
+        if xfb2:
+            g2 = d_out
+            grp, xd2 = self._bn_bwd(pfx + ".bn2", d_out, None, raw2, d_raw2, prereduced=True, xf=True)
+        elif pre2:
+            g2 = d_out
+            grp = self._bn_bwd(pfx + ".bn2", d_out, None, raw2, d_raw2, prereduced=True)
+        else:
+            g2 = E(B, Ho, Ho, pl)
+            self.tensors[pfx + ".g2"] = g2
+            grp = self._bn_bwd(pfx + ".bn2", d_out, out, raw2, d_raw2, g_out=g2)
+        grp.append(self._wgrad(L2, a1, d_raw2, Ho, Ho, Ho, Ho, 1, 1, pl, pl, pl, pl))
+        grp.append(self._unpack(L2))
+        pre1 = self._fusable(L2)
+        op, _ = self._conv(L2, d_out if xfb2 else d_raw2, pl, d_a1, Ho, Ho, Ho, Ho, 1, 1, w=L2.wd, rows=L2.rows_d, cin=L2.cin_d, cout=pl,
+                           bnb=(pfx + ".bn1", raw1, None, True) if pre1 else None, xf=xd2)
+        grp.append(op)
+        if xfb1:
+            ops1, xd1 = self._bn_bwd(pfx + ".bn1", d_a1, a1, raw1, d_raw1, affine_mask=True, prereduced=True, xf=True)
+            grp += ops1
+        else:
+            grp += self._bn_bwd(pfx + ".bn1", d_a1, a1, raw1, d_raw1, affine_mask=True, prereduced=pre1)
+        grp.append(self._wgrad(L1, x, d_raw1, Hc, Hc, Ho, Ho, stride, 1, inpl, pl, inpl, pl))
+        grp.append(self._unpack(L1))
+        if Ld is not None:
+            d_rawd, d_xd = E(B, Ho, Ho, pl), E(B, Hc, Hc, inpl)
+            self.tensors.update({pfx + ".d_rawd": d_rawd, pfx + ".d_xd": d_xd})
+            grp += self._bn_bwd(pfx + ".downsample.1", g2, None, rawd, d_rawd)
+            grp.append(self._wgrad(Ld, x, d_rawd, Hc, Hc, Ho, Ho, stride, 0, inpl, pl, inpl, pl, defer=li >= 3))
+            grp.append(self._unpack(Ld))
+            pbn = f"backbone.layer{li - 1}.{RESNET34_LAYERS[li - 2] - 1}.bn2"
+            # (r6) conv1's data gradient, the shortcut conv's data gradient and the previous block's ReLU mask + bn2-backward sums as
+            # ONE launch of the parity-class kernel: no d_xd tensor (three quarters zeros), no addend pass
+            s2d = self._s2d(L1, d_raw1, d_x, Ho, Hc, inpl, Ld=Ld, dyd=d_rawd, bnb=(pbn, prev_raw2, x)) if e.gemm_bnb else None
+            if s2d is not None:
+                grp.append(s2d)
+                del self.tensors[pfx + ".d_xd"]
+            else:
+                op, _ = self._conv(Ld, d_rawd, pl, d_xd, Ho, Ho, Hc, Hc, 2, 0, mode=1, w=Ld.wd, rows=Ld.rows_d, cin=Ld.cin_d, cout=inpl)
+                grp.append(op)
+                # d_x = gradient w.r.t. the previous layer's last block output (mask = x): its bn2 backward is reduced here
+                op, _ = self._conv(L1, d_raw1, pl, d_x, Ho, Ho, Hc, Hc, 2, 1, mode=1, w=L1.wd, rows=L1.rows_d, cin=L1.cin_d,
+                                   cout=inpl, addend=d_xd, add_cs=inpl, bnb=(pbn, prev_raw2, x, False) if e.gemm_bnb else None)
+                grp.append(op)
+        elif need_dx:
+            # previous block of the same layer: d_x is the gradient w.r.t. its output (mask = x, stored) and
+            # feeds its bn2 backward (raw input prev_raw2)
+            fuse_prev = b >= 1 and self._fusable(L1)
+            op, _ = self._conv(L1, d_a1 if xfb1 else d_raw1, pl, d_x, Ho, Ho, Hc, Hc, 1, 1, w=L1.wd, rows=L1.rows_d, cin=L1.cin_d, cout=inpl,
+                               addend=g2, add_cs=pl,
+                               bnb=(f"backbone.layer{li}.{b - 1}.bn2", prev_raw2, x, False) if fuse_prev else None, xf=xd1)
+            grp.append(op)
+        self.bwd_groups.append(grp)
+        c.d_x = d_out
+
+    def _head_convT(self, feat, d_feat, prev_raw2):
+        """the geometric head's ConvTranspose2d + BatchNorm + ReLU on the backbone's output (backward group 17).  Returns the head cursor."""
+        e, B, S, T, E = self.e, self.B, self.bn_train, self.has_backward, self._E
         h = "rot_head_net.features."
         LT = e.layers[h + "0"]
         rawt, h0 = E(B, 16, 16, 256), E(B, 16, 16, 256)
         self.tensors.update({h + "0.raw": rawt, h + "0.act": h0})
-        xf_first = (not FOLD) and (not HEAD_CONVS[0][2]) and self._xf_ok(e.layers[h + str(HEAD_CONVS[0][0])], 1, 16)
+        xf_first = S and (not HEAD_CONVS[0][2]) and self._xf_ok(e.layers[h + str(HEAD_CONVS[0][0])])
         # (r6) the ConvTranspose's forward pass on the parity-class kernel (8 x 8 maps: two images per tile); the generic kernel keeps odd batch sizes
-        if FOLD:
+        if not S:
             tf = self._convT_fwd(LT, h + "1", feat, h0, 8, 16, evalmode=True)
             self.fwd.append(tf[0] if tf is not None else
                             self._conv_bn_eval(LT, h + "1", feat, 512, h0, 8, 8, 16, 16, 2, 1, relu=True, mode=1, cin=512, cout=256))
@@ -1007,6 +1015,7 @@ class Plan:
             op, cp = tf if tf is not None else self._conv(LT, feat, 512, rawt, 8, 8, 16, 16, 2, 1, mode=1, cin=512, cout=256, stats=self.stats if S else None)
             self.fwd.append(op)
             self.fwd += self._bn_fwd(h + "1", rawt, cp, 256, B * 256, None if xf_first else h0)
+        d_h0 = None
         if T:
             d_h0, d_rawt = E(B, 16, 16, 256), E(B, 16, 16, 256)
             self.tensors.update({h + "0.d_act": d_h0, h + "0.d_raw": d_rawt})
@@ -1022,86 +1031,90 @@ class Plan:
                                    bnb=("backbone.layer4.2.bn2", prev_raw2, feat, False) if e.gemm_bnb else None)
             grp.append(op)
             self.bwd_groups.append(grp)
-        hx, d_hx, Hh = h0, (d_h0 if T else None), 16
-        prev_bn, prev_raw = h + "1", rawt
         # pend_h: hx = relu(bn(prev_raw)) is evaluated (and written to hx) by the next head conv while it stages its patch
         pend_h = dict(x1=rawt, xf=dict(mode=1, a=self.bn[h + "1"].scale, c=self.bn[h + "1"].shift, relu=True)) if xf_first else None
-        up_next = False
-        for hi, (ci, bi, up) in enumerate(HEAD_CONVS):
-            Lc = e.layers[h + str(ci)]
-            grp = []
-            fused_up, pre_sums = bool(up and up_next), False
-            if up:
-                assert pend_h is None
-                u = E(B, 2 * Hh, 2 * Hh, 256)
-                self.tensors[h + f"{ci}.up"] = u
-                sp_ = self.bn.get(prev_bn)
-                if fused_up:
-                    # (r6) BatchNorm + ReLU of the previous conv evaluated by the upsampling itself (its activation tensor is never stored), and
-                    # in the backward pass the upsampling's adjoint also reduces that BatchNorm's backward sums: two launches and two tensor
-                    # round trips less per upsampling
-                    self.fwd.append(lambda st, ctx, r_=prev_raw, sp_=sp_, u=u, Hh=Hh: check(
-                        lib.gdrn_bn_relu_upsample2x_fwd(ptr(r_), ptr(sp_.scale), ptr(sp_.shift), ptr(u), B, Hh, Hh, 256, e.dt, st), "bn_relu_upsample_fwd"))
-                else:
-                    self.fwd.append(lambda st, ctx, hx=hx, u=u, Hh=Hh: check(lib.gdrn_upsample2x_fwd(ptr(hx), ptr(u), B, Hh, Hh, 256, e.dt, st), "upsample_fwd"))
-                if T:
-                    d_u = E(B, 2 * Hh, 2 * Hh, 256)
-                    self.tensors[h + f"{ci}.d_up"] = d_u
-                    if fused_up:
-                        up_bwd = (lambda st, ctx, d_u=d_u, d_hx=d_hx, Hh=Hh, r_=prev_raw, sp_=sp_: check(
-                            lib.gdrn_upsample2x_bwd_bnsums(ptr(d_u), ptr(d_hx), ptr(r_), ptr(sp_.mean), ptr(sp_.invstd), ptr(sp_.scale), ptr(sp_.shift), B, Hh, Hh,
-                                                           256, ptr(self.stats), e.dt, st), "upsample_bwd_bnsums"))
-                    else:
-                        up_bwd = (lambda st, ctx, d_u=d_u, d_hx=d_hx, Hh=Hh: check(lib.gdrn_upsample2x_bwd(ptr(d_u), ptr(d_hx), B, Hh, Hh, 256, e.dt, st), "upsample_bwd"))
-                    d_in = d_u
-                xin, Hh = u, 2 * Hh
+        return NS(hx=h0, d_hx=d_h0, Hh=16, prev_bn=h + "1", prev_raw=rawt, pend_h=pend_h, up_next=False)
+
+    def _head_conv(self, c, hi):
+        """head conv hi of HEAD_CONVS (3x3, 256 channels, BatchNorm, ReLU; an upsampling in front of two of them) behind the head cursor c"""
+        e, lib, B, S, T, E = self.e, self.e.lib, self.B, self.bn_train, self.has_backward, self._E
+        h = "rot_head_net.features."
+        ci, bi, up = HEAD_CONVS[hi]
+        hx, d_hx, Hh, prev_bn, prev_raw, pend_h = c.hx, c.d_hx, c.Hh, c.prev_bn, c.prev_raw, c.pend_h
+        Lc = e.layers[h + str(ci)]
+        grp = []
+        fused_up = bool(up and c.up_next)
+        xin, d_in, up_bwd = hx, d_hx, None
+        if up:
+            assert pend_h is None
+            u = E(B, 2 * Hh, 2 * Hh, 256)
+            self.tensors[h + f"{ci}.up"] = u
+            sp_ = self.bn.get(prev_bn)
+            if fused_up:
+                # (r6) BatchNorm + ReLU of the previous conv evaluated by the upsampling itself (its activation tensor is never stored), and
+                # in the backward pass the upsampling's adjoint also reduces that BatchNorm's backward sums: two launches and two tensor
+                # round trips less per upsampling
+                self.fwd.append(_launch(lib.gdrn_bn_relu_upsample2x_fwd, "bn_relu_upsample_fwd", (prev_raw, sp_.scale, sp_.shift, u, B, Hh, Hh, 256, e.dt)))
             else:
-                xin = hx
-                d_in = d_hx
-                up_bwd = None
-            raw, act = E(B, Hh, Hh, 256), E(B, Hh, Hh, 256)
-            self.tensors[h + f"{ci}.raw"] = raw
-            nxt = HEAD_CONVS[hi + 1] if hi + 1 < len(HEAD_CONVS) else None
-            # this conv's BatchNorm + ReLU is applied by the next head conv on load when no upsampling sits in between
-            xf_next = (not FOLD) and nxt is not None and not nxt[2] and self._xf_ok(e.layers[h + str(nxt[0])], 1, Hh)
-            # the NEXT conv sits behind an upsampling that applies this conv's BatchNorm + ReLU itself (see `fused_up` above)
-            up_next = (not FOLD) and S and e.fuse_up and nxt is not None and nxt[2] and (T or not WL)
-            if FOLD:
-                self.fwd.append(self._conv_bn_eval(Lc, h + str(bi), xin, 256, act, Hh, Hh, Hh, Hh, 1, 1, relu=True))
-            else:
-                op, cp = self._conv(Lc, pend_h["x1"] if pend_h else xin, 256, raw, Hh, Hh, Hh, Hh, 1, 1, stats=self.stats if S else None,
-                                    xf=dict(pend_h["xf"], out=xin) if pend_h else None)
-                self.fwd.append(op)
-                self.fwd += self._bn_fwd(h + str(bi), raw, cp, 256, B * Hh * Hh, None if (xf_next or up_next) else act)
-            if not up_next:
-                self.tensors[h + f"{ci}.act"] = act   # (behind a fused upsampling the activation is never stored)
+                self.fwd.append(_launch(lib.gdrn_upsample2x_fwd, "upsample_fwd", (hx, u, B, Hh, Hh, 256, e.dt)))
             if T:
-                d_act, d_raw = E(B, Hh, Hh, 256), E(B, Hh, Hh, 256)
-                self.tensors.update({h + f"{ci}.d_act": d_act, h + f"{ci}.d_raw": d_raw})
-                # d_act is produced by the NEXT head conv's data gradient; when no upsampling sits in between, that
-                # launch masks it and reduces this BN's backward sums
-                pre = (not nxt[2] and self._fusable(e.layers[h + str(nxt[0])])) if nxt is not None else e.gemm_bnb  # (last conv: the 1x1 output conv's data gradient)
-                xfb = self._xf_ok(Lc, 3 if pre else 4, Hh)  # this BN's backward apply inside Lc's data-gradient launch (mode 3, or 4 = with the ReLU mask)
-                xd = None
-                sd_ = bool(up_next and not pre)   # the fused upsampling's adjoint behind this conv has reduced this BatchNorm's backward sums
-                if xfb:
-                    ops, xd = self._bn_bwd(h + str(bi), d_act, act, raw, d_raw, affine_mask=True, prereduced=pre, xf=True, sums_done=sd_)
-                    grp += ops
+                d_in = E(B, 2 * Hh, 2 * Hh, 256)
+                self.tensors[h + f"{ci}.d_up"] = d_in
+                if fused_up:
+                    up_bwd = _launch(lib.gdrn_upsample2x_bwd_bnsums, "upsample_bwd_bnsums",
+                                     (d_in, d_hx, prev_raw, sp_.mean, sp_.invstd, sp_.scale, sp_.shift, B, Hh, Hh, 256, self.stats, e.dt))
                 else:
-                    grp += self._bn_bwd(h + str(bi), d_act, act, raw, d_raw, affine_mask=True, prereduced=pre, sums_done=sd_)
-                grp.append(self._wgrad(Lc, xin, d_raw, Hh, Hh, Hh, Hh, 1, 1, 256, 256, 256, 256))
-                grp.append(self._unpack(Lc))
-                fuse_in = (not up) and self._fusable(Lc)  # d_in is the gradient w.r.t. the previous BN+ReLU's output
-                op, _ = self._conv(Lc, d_act if xfb else d_raw, 256, d_in, Hh, Hh, Hh, Hh, 1, 1, w=Lc.wd, rows=Lc.rows_d, cin=256, cout=256,
-                                   bnb=(prev_bn, prev_raw, None, True) if fuse_in else None, xf=xd)
-                grp.append(op)
-                if up_bwd is not None:
-                    grp.append(up_bwd)
-                self.bwd_groups.append(grp)
-                d_hx = d_act
-            pend_h = dict(x1=raw, xf=dict(mode=1, a=self.bn[h + str(bi)].scale, c=self.bn[h + str(bi)].shift, relu=True)) if xf_next else None
-            hx, prev_bn, prev_raw = act, h + str(bi), raw
-        assert pend_h is None
+                    up_bwd = _launch(lib.gdrn_upsample2x_bwd, "upsample_bwd", (d_in, d_hx, B, Hh, Hh, 256, e.dt))
+            xin, Hh = u, 2 * Hh
+        raw, act = E(B, Hh, Hh, 256), E(B, Hh, Hh, 256)
+        self.tensors[h + f"{ci}.raw"] = raw
+        nxt = HEAD_CONVS[hi + 1] if hi + 1 < len(HEAD_CONVS) else None
+        # this conv's BatchNorm + ReLU is applied by the next head conv on load when no upsampling sits in between
+        xf_next = S and nxt is not None and not nxt[2] and self._xf_ok(e.layers[h + str(nxt[0])])
+        # the NEXT conv sits behind an upsampling that applies this conv's BatchNorm + ReLU itself (see `fused_up` above)
+        up_next = S and e.fuse_up and nxt is not None and nxt[2] and (T or not self.with_loss)
+        if not S:
+            self.fwd.append(self._conv_bn_eval(Lc, h + str(bi), xin, 256, act, Hh, Hh, Hh, Hh, 1, 1, relu=True))
+        else:
+            op, cp = self._conv(Lc, pend_h["x1"] if pend_h else xin, 256, raw, Hh, Hh, Hh, Hh, 1, 1, stats=self.stats if S else None,
+                                xf=dict(pend_h["xf"], out=xin) if pend_h else None)
+            self.fwd.append(op)
+            self.fwd += self._bn_fwd(h + str(bi), raw, cp, 256, B * Hh * Hh, None if (xf_next or up_next) else act)
+        if not up_next:
+            self.tensors[h + f"{ci}.act"] = act   # (behind a fused upsampling the activation is never stored)
+        d_act = None
+        if T:
+            d_act, d_raw = E(B, Hh, Hh, 256), E(B, Hh, Hh, 256)
+            self.tensors.update({h + f"{ci}.d_act": d_act, h + f"{ci}.d_raw": d_raw})
+            # d_act is produced by the NEXT head conv's data gradient; when no upsampling sits in between, that
+            # launch masks it and reduces this BN's backward sums
+            pre = (not nxt[2] and self._fusable(e.layers[h + str(nxt[0])])) if nxt is not None else e.gemm_bnb  # (last conv: the 1x1 output conv's data gradient)
+            xfb = self._xf_ok(Lc)  # this BN's backward apply inside Lc's data-gradient launch (mode 3, or 4 = with the ReLU mask)
+            xd = None
+            sd_ = bool(up_next and not pre)   # the fused upsampling's adjoint behind this conv has reduced this BatchNorm's backward sums
+            if xfb:
+                ops, xd = self._bn_bwd(h + str(bi), d_act, act, raw, d_raw, affine_mask=True, prereduced=pre, xf=True, sums_done=sd_)
+                grp += ops
+            else:
+                grp += self._bn_bwd(h + str(bi), d_act, act, raw, d_raw, affine_mask=True, prereduced=pre, sums_done=sd_)
+            grp.append(self._wgrad(Lc, xin, d_raw, Hh, Hh, Hh, Hh, 1, 1, 256, 256, 256, 256))
+            grp.append(self._unpack(Lc))
+            fuse_in = (not up) and self._fusable(Lc)  # d_in is the gradient w.r.t. the previous BN+ReLU's output
+            op, _ = self._conv(Lc, d_act if xfb else d_raw, 256, d_in, Hh, Hh, Hh, Hh, 1, 1, w=Lc.wd, rows=Lc.rows_d, cin=256, cout=256,
+                               bnb=(prev_bn, prev_raw, None, True) if fuse_in else None, xf=xd)
+            grp.append(op)
+            if up_bwd is not None:
+                grp.append(up_bwd)
+            self.bwd_groups.append(grp)
+        c.pend_h = dict(x1=raw, xf=dict(mode=1, a=self.bn[h + str(bi)].scale, c=self.bn[h + str(bi)].shift, relu=True)) if xf_next else None
+        c.hx, c.d_hx, c.Hh, c.prev_bn, c.prev_raw, c.up_next = act, d_act, Hh, h + str(bi), raw, up_next
+
+    def _head_out(self, c):
+        """the head's 1x1 output conv and the head tail (logits -> Patch-PnP input; with losses also the map-loss sums) behind the head
+        cursor c (backward group 24)"""
+        e, lib, B, T, WL, E = self.e, self.e.lib, self.B, self.has_backward, self.with_loss, self._E
+        h, nreg = "rot_head_net.features.", e.nreg
+        hx, d_hx, prev_bn, prev_raw = c.hx, c.d_hx, c.prev_bn, c.prev_raw
         LO = e.layers[h + "23"]
         M = B * 64 * 64
         self.hs = 72
@@ -1117,13 +1130,16 @@ class Plan:
         self.pnp_in = e._zeros(M, 128)   # channels >= 5 + nreg stay zero (PREZEROED: the kernels do not re-write the pad)
         self.keep.append(self.pnp_in)
         self.tensors.update({"head_out": self.head_out, "pnp_in": self.pnp_in})
-        if fused_tail and WL:
-            self.acc_rows = int(lib.gdrn_head_conv_tail_loss_rows(B, 4096))
-            assert self.acc_rows > 0
+        if WL:
+            # map-loss sums: totals in acc[0..7], behind them one partial row per workgroup of the kernel (ACC_ROWS: stored, then added in a fixed
+            # order by gdrn_loss_finalize -- no memset launch, no atomics, run-to-run identical losses)
+            self.acc_rows = int(lib.gdrn_head_conv_tail_loss_rows(B, 4096) if fused_tail else lib.gdrn_head_tail_loss_rows(B, 4096, nreg, self.hs, 128))
+            if self.acc_rows <= 0:
+                check(self.acc_rows or -1, "head_tail_loss_rows")
             self.acc = E(8 + 8 * self.acc_rows, dtype=torch.float64)
             self.losses = e._zeros(8, dtype=F32t)
-
-            def head_conv_tail(st, ctx, hx=hx):
+        if fused_tail and WL:
+            def head_conv_tail(st, ctx):
                 check(lib.gdrn_head_conv_tail_loss_fwd(ptr(hx), 256, ptr(LO.wf), LO.rows_f, ptr(bias_o), ctx["coord2d"], ctx["extents"], ptr(self.head_out), self.hs,
                                                        ptr(self.pnp_in), 128, ctx["gt_xyz"], ctx["mask_visib"], ctx["mask_trunc"], ctx["gt_region"], ptr(self.acc),
                                                        B, 4096, nreg, e.dt | PREZEROED, st), "head_conv_tail_loss_fwd")
@@ -1131,7 +1147,7 @@ class Plan:
             head_conv_tail.meta = dict(kernel="head_conv_tail64_kernel<bf16,true>", flops=2.0 * M * 256 * e.head_c, layer=h + "23+tail+losses")
             self.fwd.append(head_conv_tail)
         elif fused_tail:
-            def head_conv_tail(st, ctx, hx=hx):
+            def head_conv_tail(st, ctx):
                 # ctx["want_maps"] False (GDRN.forward without cfg.TEST.USE_PNP): nobody reads the logits -- head = NULL saves their 75 MB at bs = 64
                 # (head_valid: does plan.head_out hold THIS forward's logits?  readers -- GDRN._maps, tools -- assert it: ADVICE r5)
                 self.head_valid = bool(ctx.get("want_maps", True))
@@ -1142,201 +1158,182 @@ class Plan:
             head_conv_tail.meta = dict(kernel="head_conv_tail64_kernel<bf16,false>", flops=2.0 * M * 256 * e.head_c, layer=h + "23+tail")
             self.fwd.append(head_conv_tail)
         elif WL:
-            # map-loss sums: totals in acc[0..7], behind them one partial row per workgroup of the kernel (ACC_ROWS: stored, then added in a fixed
-            # order by map_loss_finalize_rows -- no memset launch, no atomics, run-to-run identical losses)
-            rows_on = True
-            self.acc_rows = int(lib.gdrn_head_tail_loss_rows(B, 4096, nreg, self.hs, 128)) if rows_on else 0
-            if rows_on and self.acc_rows <= 0:
-                check(self.acc_rows or -1, "head_tail_loss_rows")
-            self.acc = E(8 + 8 * self.acc_rows, dtype=torch.float64)
-            self.losses = e._zeros(8, dtype=F32t)
             # head tail + map-loss sums in one pass over the logits (train mode)
             self.fwd.append(lambda st, ctx: check(lib.gdrn_head_tail_loss_fwd(ptr(self.head_out), self.hs, ctx["coord2d"], ctx["extents"], ptr(self.pnp_in), 128,
                                                                               ctx["gt_xyz"], ctx["mask_visib"], ctx["mask_trunc"], ctx["gt_region"], ptr(self.acc),
-                                                                              B, 4096, nreg, e.dt | PREZEROED | (ACC_ROWS if self.acc_rows else 0), st), "head_tail_loss_fwd"))
+                                                                              B, 4096, nreg, e.dt | PREZEROED | ACC_ROWS, st), "head_tail_loss_fwd"))
         else:
             self.fwd.append(lambda st, ctx: check(lib.gdrn_head_tail_fwd(ptr(self.head_out), self.hs, ctx["coord2d"], ctx["extents"],
                                                                          ptr(self.pnp_in), 128, B, 4096, nreg, e.dt | PREZEROED, st), "head_tail_fwd"))
-        if T:
-            self.d_head = e._zeros(M, 128)   # pad channels zero-filled once (PREZEROED)
-            self.keep.append(self.d_head)
-            self.d_pnp_in = E(M, 128)
-            self.gw = e._zeros(8, dtype=F32t)
-            self.tensors.update({"d_head": self.d_head, "d_pnp_in": self.d_pnp_in})
-            grp = [lambda st, ctx: check(lib.gdrn_head_tail_bwd(ptr(self.head_out), self.hs, ptr(self.pnp_in), ptr(self.d_pnp_in), 128,
-                                                                ctx["extents"], ctx["gt_xyz"], ctx["mask_visib"], ctx["mask_trunc"],
-                                                                ctx["gt_region"], ptr(self.acc), ptr(self.gw), ptr(self.d_head), 128, B,
-                                                                4096, nreg, e.dt | PREZEROED, st), "head_tail_bwd")]
-            grp.append(self._wgrad(LO, hx, self.d_head, 64, 64, 64, 64, 1, 0, 256, e.head_c, 256, 128))
-            grp.append(self._unpack(LO))
-            gb = e.grads[h + "23.bias"]
-            self.grad_group[h + "23.bias"] = len(self.bwd_groups)
-            self._zero_regions.append(self._grad16(gb))
-            grp.append(self._side(lambda st, ctx: check(lib.gdrn_bias_grad(ptr(self.d_head), 128, M, e.head_c, ptr(gb), e.dt | PREZEROED, st), "bias_grad")))
-            if e.h16 and e.gemm_bnb:
-                # the 1x1 output conv's data gradient on its own kernel (K = 69: the generic 128 x 128 tile ran it at 83 TFLOP/s), with the ReLU mask and
-                # the BatchNorm-backward sums of the head's last BatchNorm in the epilogue as the generic kernel's bnb_* epilogue has them
-                sbp = self.bn[prev_bn]
-                nrows_h = int(lib.gdrn_head_out_dgrad_rows(B, 4096))
-                assert 0 < nrows_h and nrows_h * 2 * 256 <= self.stats.numel()
+        if not T:
+            return
+        self.d_head = e._zeros(M, 128)   # pad channels zero-filled once (PREZEROED)
+        self.keep.append(self.d_head)
+        self.d_pnp_in = E(M, 128)
+        self.gw = e._zeros(8, dtype=F32t)
+        self.tensors.update({"d_head": self.d_head, "d_pnp_in": self.d_pnp_in})
+        grp = [lambda st, ctx: check(lib.gdrn_head_tail_bwd(ptr(self.head_out), self.hs, ptr(self.pnp_in), ptr(self.d_pnp_in), 128,
+                                                            ctx["extents"], ctx["gt_xyz"], ctx["mask_visib"], ctx["mask_trunc"],
+                                                            ctx["gt_region"], ptr(self.acc), ptr(self.gw), ptr(self.d_head), 128, B,
+                                                            4096, nreg, e.dt | PREZEROED, st), "head_tail_bwd")]
+        grp.append(self._wgrad(LO, hx, self.d_head, 64, 64, 64, 64, 1, 0, 256, e.head_c, 256, 128))
+        grp.append(self._unpack(LO))
+        gb = e.grads[h + "23.bias"]
+        self.grad_group[h + "23.bias"] = len(self.bwd_groups)
+        self._zero_regions.append(self._grad16(gb))
+        grp.append(self._side(_launch(lib.gdrn_bias_grad, "bias_grad", (self.d_head, 128, M, e.head_c, gb, e.dt | PREZEROED))))
+        if e.h16 and e.gemm_bnb:
+            # the 1x1 output conv's data gradient on its own kernel (K = 69: the generic 128 x 128 tile ran it at 83 TFLOP/s), with the ReLU mask and
+            # the BatchNorm-backward sums of the head's last BatchNorm in the epilogue as the generic kernel's bnb_* epilogue has them
+            sbp = self.bn[prev_bn]
+            nrows_h = int(lib.gdrn_head_out_dgrad_rows(B, 4096))
+            assert 0 < nrows_h and nrows_h * 2 * 256 <= self.stats.numel()
+            head_dgrad = _launch(lib.gdrn_head_out_dgrad, "head_out_dgrad", (self.d_head, 128, LO.wd, LO.cin_d, prev_raw, 256, sbp.mean, sbp.invstd, sbp.scale,
+                                                                             sbp.shift, d_hx, 256, self.stats, B, 4096, e.dt))
+            coef_h = self._bn_coef_op(prev_bn, self.stats, nrows_h)
 
-                def head_dgrad(st, ctx, d_hx=d_hx, prev_raw=prev_raw, sbp=sbp):
-                    check(lib.gdrn_head_out_dgrad(ptr(self.d_head), 128, ptr(LO.wd), LO.cin_d, ptr(prev_raw), 256, ptr(sbp.mean), ptr(sbp.invstd), ptr(sbp.scale),
-                                                  ptr(sbp.shift), ptr(d_hx), 256, ptr(self.stats), B, 4096, e.dt, st), "head_out_dgrad")
+            def op(st, ctx):
+                head_dgrad(st, ctx)
+                coef_h(st, ctx)
 
-                coef_h = self._bn_coef_op(prev_bn, self.stats, nrows_h)
+            op.parts = (head_dgrad, coef_h)
+            op.meta = dict(kernel="head_out_dgrad64_kernel<bf16>", flops=2.0 * M * 256 * e.head_c, bytes=float(M * (128 + 256 + 256) * 2), layer=h + "23:dgrad")
+        else:
+            op, _ = self._conv(LO, self.d_head, 128, d_hx, 64, 64, 64, 64, 1, 0, w=LO.wd, rows=LO.rows_d, cin=128, cout=256,
+                               bnb=(prev_bn, prev_raw, None, True) if e.gemm_bnb else None)
+        grp.append(op)
+        self.bwd_groups.append(grp)
 
-                def op(st, ctx):
-                    head_dgrad(st, ctx)
-                    coef_h(st, ctx)
-
-                op.parts = (head_dgrad, coef_h)
-                op.meta = dict(kernel="head_out_dgrad64_kernel<bf16>", flops=2.0 * M * 256 * e.head_c, bytes=float(M * (128 + 256 + 256) * 2), layer=h + "23:dgrad")
-            else:
-                op, _ = self._conv(LO, self.d_head, 128, d_hx, 64, 64, 64, 64, 1, 0, w=LO.wd, rows=LO.rows_d, cin=128, cout=256,
-                                   bnb=(prev_bn, prev_raw, None, True) if e.gemm_bnb else None)
+    def _pnp_conv(self, c, ci, gi):
+        """Patch-PnP conv ci (3x3 stride 2) + GroupNorm gi + ReLU behind the Patch-PnP cursor c"""
+        e, lib, B, E = self.e, self.e.lib, self.B, self._E
+        q = "pnp_net.features."
+        px, d_px, Hp, cin = c.px, c.d_px, c.Hp, c.cin
+        Lc = e.layers[q + str(ci)]
+        Ho = Hp // 2
+        r, gact = E(B, Ho, Ho, 128), E(B, Ho, Ho, 128)
+        mr = E(B, 32, 2, dtype=F32t)
+        self.tensors.update({q + f"{ci}.raw": r, q + f"{ci}.act": gact})
+        s2op = self._s2(Lc, px, cin, r, Hp, Ho) if cin == Lc.cin_f else None   # (r6: the parity-plane kernel on the 64 -> 32 and 32 -> 16 convs)
+        if s2op is not None:
+            op = s2op[0]
+        else:
+            op, _ = self._conv(Lc, px, cin, r, Hp, Hp, Ho, Ho, 2, 1, cin=cin, cout=128)
+        self.fwd.append(op)
+        gam, bet = e.P[q + f"{gi}.weight"], e.P[q + f"{gi}.bias"]
+        self.fwd.append(_launch(lib.gdrn_gn_relu_fwd, "gn_relu_fwd", (r, gam, bet, gact, mr, B, Ho * Ho, 128, 32, 1e-5, e.dt)))
+        d_g = None
+        if self.has_backward:
+            d_g, d_r = E(B, Ho, Ho, 128), E(B, Ho, Ho, 128)
+            self.tensors.update({q + f"{ci}.d_act": d_g, q + f"{ci}.d_raw": d_r})
+            dgam, dbet = e.grads[q + f"{gi}.weight"], e.grads[q + f"{gi}.bias"]
+            self.grad_group[q + f"{gi}.weight"] = self.grad_group[q + f"{gi}.bias"] = len(self.bwd_groups)
+            grp = [_launch(lib.gdrn_gn_relu_bwd, "gn_relu_bwd", (d_g, gact, r, gam, mr, d_r, dgam, dbet, B, Ho * Ho, 128, 32, e.dt | PREZEROED))]
+            self._zero_regions += [self._grad16(dgam), self._grad16(dbet)]
+            grp.append(self._wgrad(Lc, px, d_r, Hp, Hp, Ho, Ho, 2, 1, cin, 128, cin, 128))
+            grp.append(self._unpack(Lc))
+            op = self._s2d(Lc, d_r, d_px, Ho, Hp, cin) if cin == Lc.cin_f else None   # (r6: the parity-class kernel where it covers the map)
+            if op is None:
+                op, _ = self._conv(Lc, d_r, 128, d_px, Ho, Ho, Hp, Hp, 2, 1, mode=1, w=Lc.wd, rows=Lc.rows_d, cin=128, cout=cin)
             grp.append(op)
             self.bwd_groups.append(grp)
+        c.px, c.d_px, c.Hp, c.cin = gact, d_g, Ho, 128
 
-        # ---------------- Patch-PnP
-        q = "pnp_net.features."
-        px, d_px, Hp, cin = self.pnp_in, (self.d_pnp_in if T else None), 64, 128
-        for ci, gi in ((0, 1), (3, 4), (6, 7)):
-            Lc = e.layers[q + str(ci)]
-            Ho = Hp // 2
-            r, gact = E(B, Ho, Ho, 128), E(B, Ho, Ho, 128)
-            mr = E(B, 32, 2, dtype=F32t)
-            self.tensors.update({q + f"{ci}.raw": r, q + f"{ci}.act": gact})
-            s2op = self._s2(Lc, px, cin, r, Hp, Ho) if cin == Lc.cin_f else None   # (r6: the parity-plane kernel on the 64 -> 32 and 32 -> 16 convs)
-            if s2op is not None:
-                op = s2op[0]
-            else:
-                op, _ = self._conv(Lc, px, cin, r, Hp, Hp, Ho, Ho, 2, 1, cin=cin, cout=128)
-            self.fwd.append(op)
-            gam, bet = e.P[q + f"{gi}.weight"], e.P[q + f"{gi}.bias"]
-            self.fwd.append(lambda st, ctx, r=r, gam=gam, bet=bet, gact=gact, mr=mr, Ho=Ho: check(
-                lib.gdrn_gn_relu_fwd(ptr(r), ptr(gam), ptr(bet), ptr(gact), ptr(mr), B, Ho * Ho, 128, 32, 1e-5, e.dt, st), "gn_relu_fwd"))
-            if T:
-                d_g, d_r = E(B, Ho, Ho, 128), E(B, Ho, Ho, 128)
-                self.tensors.update({q + f"{ci}.d_act": d_g, q + f"{ci}.d_raw": d_r})
-                dgam, dbet = e.grads[q + f"{gi}.weight"], e.grads[q + f"{gi}.bias"]
-                self.grad_group[q + f"{gi}.weight"] = self.grad_group[q + f"{gi}.bias"] = len(self.bwd_groups)
-                grp = [lambda st, ctx, d_g=d_g, gact=gact, r=r, gam=gam, mr=mr, d_r=d_r, dgam=dgam, dbet=dbet, Ho=Ho: check(
-                    lib.gdrn_gn_relu_bwd(ptr(d_g), ptr(gact), ptr(r), ptr(gam), ptr(mr), ptr(d_r), ptr(dgam), ptr(dbet), B, Ho * Ho, 128, 32,
-                                         e.dt | PREZEROED, st), "gn_relu_bwd")]
-                self._zero_regions += [self._grad16(dgam), self._grad16(dbet)]
-                grp.append(self._wgrad(Lc, px, d_r, Hp, Hp, Ho, Ho, 2, 1, cin, 128, cin, 128))
-                grp.append(self._unpack(Lc))
-                op = self._s2d(Lc, d_r, d_px, Ho, Hp, cin) if cin == Lc.cin_f else None   # (r6: the parity-class kernel where it covers the map)
-                if op is None:
-                    op, _ = self._conv(Lc, d_r, 128, d_px, Ho, Ho, Hp, Hp, 2, 1, mode=1, w=Lc.wd, rows=Lc.rows_d, cin=128, cout=cin)
-                grp.append(op)
-                self.bwd_groups.append(grp)
-                d_px = d_g
-            px, Hp, cin = gact, Ho, 128
-        g2act, d_g2 = px, d_px
+    def _fc_fwd(self, g2act):
+        """fc1, fc2 and fc_r | fc_t on the last Patch-PnP activation g2act.  Returns the activations (f1, f2)."""
+        e, lib, B, E = self.e, self.e.lib, self.B, self._E
         L1, L2, L3 = e.layers["pnp_net.fc1"], e.layers["pnp_net.fc2"], e.layers["pnp_net.fc_rt"]
         f1, f2 = E(B, 1024), E(B, 256)
         self.fc_out = e._zeros(B, 64, dtype=F32t)   # (columns 9 .. 63 are never written)
         self.keep.append(self.fc_out)
         self.tensors.update({"pnp_net.fc1.act": f1, "pnp_net.fc2.act": f2, "fc_out": self.fc_out})
         b1, b2 = e.P["pnp_net.fc1.bias"], e.P["pnp_net.fc2.bias"]
-        if e.h16 and B <= 64 and e.fc_splitk:
+        if e.h16 and B <= 64:
             # fc1 is bound by reading its 16.8 MB of weights once: split-K skinny GEMM instead of 8 gather workgroups.
             # L1.wf = [1024 rows][64 taps][128 ch] = row-major [N][K] in the (pixel, channel) order of the NHWC input
             ws1 = e._zeros(16 * B * 1024 + 64, dtype=F32t)  # GDRN_LINEAR_MAX_SPLITS slabs + tickets
             self.keep.append(ws1)
-
-            def fc1_fwd(st, ctx):
-                check(lib.gdrn_linear_splitk(ptr(g2act), ptr(L1.wf), ptr(b1), ptr(f1), B, 8192, 1024, 8192, 8192, 1024, 2, ptr(ws1), e.dt, st),
-                      "linear_splitk fc1")
-
-            fc1_fwd.meta = dict(kernel="linear_splitk_kernel", flops=2.0 * B * 8192 * 1024, layer="pnp_net.fc1")
-            self.fwd.append(fc1_fwd)
-        else:
-            op, _ = self._conv(L1, g2act, 128, f1, 8, 8, 1, 1, 1, 0, bias=b1, act=2, cin=128, cout=1024)
-            self.fwd.append(op)
-        if e.h16 and B <= 64 and e.fc_splitk:
+            self.fwd.append(_launch(lib.gdrn_linear_splitk, "linear_splitk fc1", (g2act, L1.wf, b1, f1, B, 8192, 1024, 8192, 8192, 1024, 2, ws1, e.dt),
+                                    dict(kernel="linear_splitk_kernel", flops=2.0 * B * 8192 * 1024, layer="pnp_net.fc1")))
             # fc2 (64 x 1024 -> 256) on the gather kernel is two workgroups walking K = 1024 serially (20 us for 34 MFLOP): the same split-K
             # kernel, 16 column tiles x 8 K ranges (r4)
             ws2 = e._zeros(16 * B * 256 + 64, dtype=F32t)
             self.keep.append(ws2)
-
             # (r6) fc2's finish pass (bias, LeakyReLU), fc_r | fc_t and the pose decode are ONE launch (gdrn_pose_loss, fc2_ws): fc2 leaves its slabs
             self.fc_tail = (ws2, int(lib.gdrn_linear_splits(1024, 256))) if e.fc_tail else None
-            act2 = -1 if self.fc_tail else 2
-
-            def fc2_fwd(st, ctx):
-                check(lib.gdrn_linear_splitk(ptr(f1), ptr(L2.wf), ptr(b2), ptr(f2), B, 1024, 256, 1024, 1024, 256, act2, ptr(ws2), e.dt, st),
-                      "linear_splitk fc2")
-
-            fc2_fwd.meta = dict(kernel="linear_splitk_kernel", flops=2.0 * B * 1024 * 256, layer="pnp_net.fc2")
-            self.fwd.append(fc2_fwd)
+            self.fwd.append(_launch(lib.gdrn_linear_splitk, "linear_splitk fc2",
+                                    (f1, L2.wf, b2, f2, B, 1024, 256, 1024, 1024, 256, -1 if self.fc_tail else 2, ws2, e.dt),
+                                    dict(kernel="linear_splitk_kernel", flops=2.0 * B * 1024 * 256, layer="pnp_net.fc2")))
         else:
+            op, _ = self._conv(L1, g2act, 128, f1, 8, 8, 1, 1, 1, 0, bias=b1, act=2, cin=128, cout=1024)
+            self.fwd.append(op)
             op, _ = self._conv(L2, f1, 1024, f2, 1, 1, 1, 1, 1, 0, bias=b2, act=2, cin=1024, cout=256)
             self.fwd.append(op)
-        if getattr(self, "fc_tail", None) is None:
+        if self.fc_tail is None:
             op, _ = self._conv(L3, f2, 256, self.fc_out, 1, 1, 1, 1, 1, 0, bias=e.rt_b, out_f32=1, cin=256, cout=9, y_cs=64)
             self.fwd.append(op)
         self._fc2 = (f2, b2, L3)
-        if T:
-            self.dfc3 = e._zeros(3, B, 64, dtype=F32t)
-            d_fc32 = e._zeros(B, 64, dtype=F32t)
-            d_fc = E(B, 64)
-            d_f2, d_f2p, d_f1, d_f1p = E(B, 256), E(B, 256), E(B, 1024), E(B, 1024)
-            self.tensors.update({"d_fc": d_fc, "pnp_net.fc2.d_act": d_f2, "pnp_net.fc2.d_pre": d_f2p, "pnp_net.fc1.d_act": d_f1, "pnp_net.fc1.d_pre": d_f1p})
-            o_rt = e.grad_offsets["pnp_net.fc_r.bias"]   # the two bias gradients' shared slot of the flat gradient buffer (Engine.__init__)
-            assert e.grad_offsets["pnp_net.fc_t.bias"] == o_rt + 6 and o_rt % 4 == 0
-            self._rt_gb_full = e.grad_flat[o_rt:o_rt + 12]
-            self.rt_gb = self._rt_gb_full[:9]
-            self._zero_regions += [self._rt_gb_full, self._grad16(e.grads["pnp_net.fc1.bias"]), self._grad16(e.grads["pnp_net.fc2.bias"])]
-            g_b1, g_b2 = e.grads["pnp_net.fc1.bias"], e.grads["pnp_net.fc2.bias"]
-            for n_ in ("pnp_net.fc1.bias", "pnp_net.fc2.bias", "pnp_net.fc_r.bias", "pnp_net.fc_t.bias"):
-                self.grad_group[n_] = len(self.bwd_groups)
-            # (skipped when the forward pass was seeded: gdrn_pose_loss has then written dL/dfc itself -- ctx["seeded"], GDRN.train_step)
-            comb = lambda st, ctx: check(lib.gdrn_combine3(ptr(self.dfc3), self.gw.data_ptr() + 20, ptr(d_fc32), B * 64, st), "combine3")
-            cast = lambda st, ctx: check(lib.gdrn_cast_from_f32(ptr(d_fc32), ptr(d_fc), B * 64, e.dt, st), "cast")
-            comb.seed = cast.seed = True
-            self.d_fc = d_fc
-            grp = [
-                comb,
-                cast,
-                self._wgrad(L3, f2, d_fc, 1, 1, 1, 1, 1, 0, 256, 9, 256, 64, defer=True),
-                self._unpack(L3),
-                lambda st, ctx: check(lib.gdrn_bias_grad(ptr(d_fc), 64, B, 9, ptr(self.rt_gb), e.dt | PREZEROED, st), "bias_grad"),   # = both .grad views
-            ]
-            op, _ = self._conv(L3, d_fc, 64, d_f2, 1, 1, 1, 1, 1, 0, w=L3.wd, rows=L3.rows_d, cin=64, cout=256)
+        return f1, f2
+
+    def _fc_bwd(self, g2act, d_g2, f1, f2):
+        """backward group 28: dL/dfc from the three pose losses, then fc_r | fc_t, fc2, fc1 -- d_g2 is the gradient of g2act"""
+        e, lib, B, E = self.e, self.e.lib, self.B, self._E
+        L1, L2, L3 = e.layers["pnp_net.fc1"], e.layers["pnp_net.fc2"], e.layers["pnp_net.fc_rt"]
+        self.dfc3 = e._zeros(3, B, 64, dtype=F32t)
+        d_fc32 = e._zeros(B, 64, dtype=F32t)
+        d_fc = E(B, 64)
+        d_f2, d_f2p, d_f1, d_f1p = E(B, 256), E(B, 256), E(B, 1024), E(B, 1024)
+        self.tensors.update({"d_fc": d_fc, "pnp_net.fc2.d_act": d_f2, "pnp_net.fc2.d_pre": d_f2p, "pnp_net.fc1.d_act": d_f1, "pnp_net.fc1.d_pre": d_f1p})
+        o_rt = e.grad_offsets["pnp_net.fc_r.bias"]   # the two bias gradients' shared slot of the flat gradient buffer (Engine.__init__)
+        assert e.grad_offsets["pnp_net.fc_t.bias"] == o_rt + 6 and o_rt % 4 == 0
+        self._rt_gb_full = e.grad_flat[o_rt:o_rt + 12]
+        self.rt_gb = self._rt_gb_full[:9]
+        self._zero_regions += [self._rt_gb_full, self._grad16(e.grads["pnp_net.fc1.bias"]), self._grad16(e.grads["pnp_net.fc2.bias"])]
+        g_b1, g_b2 = e.grads["pnp_net.fc1.bias"], e.grads["pnp_net.fc2.bias"]
+        for n_ in ("pnp_net.fc1.bias", "pnp_net.fc2.bias", "pnp_net.fc_r.bias", "pnp_net.fc_t.bias"):
+            self.grad_group[n_] = len(self.bwd_groups)
+        # (skipped when the forward pass was seeded: gdrn_pose_loss has then written dL/dfc itself -- ctx["seeded"], GDRN.train_step)
+        comb = _launch(lib.gdrn_combine3, "combine3", (self.dfc3, self.gw.data_ptr() + 20, d_fc32, B * 64))
+        cast = _launch(lib.gdrn_cast_from_f32, "cast", (d_fc32, d_fc, B * 64, e.dt))
+        comb.seed = cast.seed = True
+        self.d_fc = d_fc
+        bias_grad = lambda d, cs, n, g: _launch(lib.gdrn_bias_grad, "bias_grad", (d, cs, B, n, g, e.dt | PREZEROED))
+        grp = [
+            comb,
+            cast,
+            self._wgrad(L3, f2, d_fc, 1, 1, 1, 1, 1, 0, 256, 9, 256, 64, defer=True),
+            self._unpack(L3),
+            bias_grad(d_fc, 64, 9, self.rt_gb),   # = both .grad views
+        ]
+        op, _ = self._conv(L3, d_fc, 64, d_f2, 1, 1, 1, 1, 1, 0, w=L3.wd, rows=L3.rows_d, cin=64, cout=256)
+        grp.append(op)
+        grp.append(_launch(lib.gdrn_leaky_bwd, "leaky_bwd", (d_f2, f2, d_f2p, B * 256, e.dt)))
+        grp.append(self._wgrad(L2, f1, d_f2p, 1, 1, 1, 1, 1, 0, 1024, 256, 1024, 256, defer=True))
+        grp.append(self._unpack(L2))
+        grp.append(self._side(bias_grad(d_f2p, 256, 256, g_b2), defer=True))
+        op, _ = self._conv(L2, d_f2p, 256, d_f1, 1, 1, 1, 1, 1, 0, w=L2.wd, rows=L2.rows_d, cin=256, cout=1024)
+        grp.append(op)
+        grp.append(_launch(lib.gdrn_leaky_bwd, "leaky_bwd", (d_f1, f1, d_f1p, B * 1024, e.dt)))
+        grp.append(self._wgrad(L1, g2act, d_f1p, 8, 8, 1, 1, 1, 0, 128, 1024, 128, 1024, defer=True))
+        grp.append(self._unpack(L1))
+        grp.append(self._side(bias_grad(d_f1p, 1024, 1024, g_b1), defer=True))
+        if e.h16 and B <= 64 and e.fc_tail:
+            # (r6) fc1's data gradient is bound by reading its 16.8 MB operand once, like its forward pass: the split-K skinny GEMM (L1.wd =
+            # [8192 rows = (pixel, channel)][1024] row-major) instead of 64 gather workgroups walking K = 1024 each (39 us -> 15 + 7)
+            ws1d = e._zeros(16 * B * 8192 + 64, dtype=F32t)
+            self.keep.append(ws1d)
+            grp.append(_launch(lib.gdrn_linear_splitk, "linear_splitk fc1:dgrad", (d_f1p, L1.wd, None, d_g2, B, 1024, 8192, 1024, 1024, 8192, 0, ws1d, e.dt),
+                               dict(kernel="linear_splitk_kernel", flops=2.0 * B * 8192 * 1024, layer="pnp_net.fc1:dgrad")))
+        else:
+            op, _ = self._conv(L1, d_f1p, 1024, d_g2, 1, 1, 1, 1, 1, 0, w=L1.wd, rows=L1.rows_d, cin=1024, cout=8192, KH=1, KW=1, y_cs=8192)
             grp.append(op)
-            grp.append(lambda st, ctx: check(lib.gdrn_leaky_bwd(ptr(d_f2), ptr(f2), ptr(d_f2p), B * 256, e.dt, st), "leaky_bwd"))
-            grp.append(self._wgrad(L2, f1, d_f2p, 1, 1, 1, 1, 1, 0, 1024, 256, 1024, 256, defer=True))
-            grp.append(self._unpack(L2))
-            grp.append(self._side(lambda st, ctx: check(lib.gdrn_bias_grad(ptr(d_f2p), 256, B, 256, ptr(g_b2), e.dt | PREZEROED, st), "bias_grad"), defer=True))
-            op, _ = self._conv(L2, d_f2p, 256, d_f1, 1, 1, 1, 1, 1, 0, w=L2.wd, rows=L2.rows_d, cin=256, cout=1024)
-            grp.append(op)
-            grp.append(lambda st, ctx: check(lib.gdrn_leaky_bwd(ptr(d_f1), ptr(f1), ptr(d_f1p), B * 1024, e.dt, st), "leaky_bwd"))
-            grp.append(self._wgrad(L1, g2act, d_f1p, 8, 8, 1, 1, 1, 0, 128, 1024, 128, 1024, defer=True))
-            grp.append(self._unpack(L1))
-            grp.append(self._side(lambda st, ctx: check(lib.gdrn_bias_grad(ptr(d_f1p), 1024, B, 1024, ptr(g_b1), e.dt | PREZEROED, st), "bias_grad"), defer=True))
-            if e.h16 and B <= 64 and e.fc_splitk and e.fc_tail:
-                # (r6) fc1's data gradient is bound by reading its 16.8 MB operand once, like its forward pass: the split-K skinny GEMM (L1.wd =
-                # [8192 rows = (pixel, channel)][1024] row-major) instead of 64 gather workgroups walking K = 1024 each (39 us -> 15 + 7)
-                ws1d = e._zeros(16 * B * 8192 + 64, dtype=F32t)
-                self.keep.append(ws1d)
+        self.bwd_groups.append(grp)
 
-                def fc1_dgrad(st, ctx):
-                    check(lib.gdrn_linear_splitk(ptr(d_f1p), ptr(L1.wd), None, ptr(d_g2), B, 1024, 8192, 1024, 1024, 8192, 0, ptr(ws1d), e.dt, st),
-                          "linear_splitk fc1:dgrad")
-
-                fc1_dgrad.meta = dict(kernel="linear_splitk_kernel", flops=2.0 * B * 8192 * 1024, layer="pnp_net.fc1:dgrad")
-                grp.append(fc1_dgrad)
-            else:
-                op, _ = self._conv(L1, d_f1p, 1024, d_g2, 1, 1, 1, 1, 1, 0, w=L1.wd, rows=L1.rows_d, cin=1024, cout=8192, KH=1, KW=1, y_cs=8192)
-                grp.append(op)
-            self.bwd_groups.append(grp)
-
-        # ---------------- pose decode (+ pose / map losses in train mode)
-        self.rot = E(B, 3, 3, dtype=F32t)
-        self.trans = E(B, 3, dtype=F32t)
+    def _pose(self):
+        """pose decode (+ the pose losses and, with losses, the finalize launch of all eight) from fc_out and the per-RoI context"""
+        e, lib, B, T, WL = self.e, self.e.lib, self.B, self.has_backward, self.with_loss
+        self.rot = self._E(B, 3, 3, dtype=F32t)
+        self.trans = self._E(B, 3, dtype=F32t)
         self.vis = e._zeros(B, 2, dtype=F32t)
         self.pose_p = PoseParams()
 
@@ -1352,10 +1349,10 @@ class Plan:
             pp.losses = (self.losses.data_ptr() + 20) if WL else None
             pp.dfc = ptr(self.dfc3) if T else None
             pp.vis = ptr(self.vis) if WL else None
-            pp.loss_rows = ptr(self.pose_rows) if (WL and self.acc_rows) else None
+            pp.loss_rows = ptr(self.pose_rows)
             seeded = bool(T and WL and e.h16 and ctx.get("seeded"))   # the fused train step: dL/dloss is known now, dL/dfc leaves this launch
             pp.gw, pp.dfc_comb = ((self.gw.data_ptr() + 20), ptr(self.d_fc)) if seeded else (None, None)
-            if getattr(self, "fc_tail", None) is not None:
+            if self.fc_tail is not None:
                 f2_, b2_, L3_ = self._fc2
                 pp.fc2_ws, pp.fc2_splits, pp.fc2_bias, pp.f2_out = ptr(self.fc_tail[0]), self.fc_tail[1], ptr(b2_), ptr(f2_)
                 pp.w_rt, pp.b_rt, pp.fc_w = ptr(L3_.wf), ptr(e.rt_b), ptr(self.fc_out)
@@ -1363,13 +1360,10 @@ class Plan:
 
         self.fwd.append(pose)
         if WL:
-            if self.acc_rows:
-                self.pose_rows = E(B, 4, dtype=F32t)
-                # ctx["loss_w"] / ctx["weighted"] (device pointers, the fused train step): the weighted loss vector it returns, written here
-                self.fwd.append(lambda st, ctx: check(lib.gdrn_loss_finalize(ptr(self.acc), self.acc_rows, B, 4096, ptr(self.pose_rows), ptr(self.losses),
-                                                                             ctx.get("loss_w"), ctx.get("weighted"), st), "loss_finalize"))
-            else:
-                self.fwd.append(lambda st, ctx: check(lib.gdrn_map_loss_finalize(ptr(self.acc), B, 4096, ptr(self.losses), st), "map_loss_finalize"))
+            self.pose_rows = self._E(B, 4, dtype=F32t)
+            # ctx["loss_w"] / ctx["weighted"] (device pointers, the fused train step): the weighted loss vector it returns, written here
+            self.fwd.append(lambda st, ctx: check(lib.gdrn_loss_finalize(ptr(self.acc), self.acc_rows, B, 4096, ptr(self.pose_rows), ptr(self.losses),
+                                                                         ctx.get("loss_w"), ctx.get("weighted"), st), "loss_finalize"))
 
     # ---- execution ---------------------------------------------------------------------------
     def run_forward(self, ctx):
@@ -1405,7 +1399,7 @@ class Plan:
         # data-gradient / BatchNorm kernels (one workgroup per CU on the small feature maps) shares the CUs with it.
         side = e.side_stream() if e.wgrad_stream else None
         used_side = in_side = False
-        probe = getattr(self, "op_events", None)   # bench.py: [(start, end, meta, on_side)] HIP events around the conv launches of THIS pass
+        probe = self.op_events   # bench.py: [(start, end, meta, on_side)] HIP events around the conv launches of THIS pass
         seeded = bool(ctx.get("seeded")) and self.e.h16
         for i, op in enumerate(self.bwd):
             if seeded and getattr(op, "seed", False):
@@ -1449,7 +1443,7 @@ class Plan:
 
     def _bucket_marks(self):
         """index of the last backward op of each gradient bucket (pnp | head | layer4 | layer3 | rest)."""
-        if hasattr(self, "_marks"):
+        if self._marks is not None:
             return self._marks
         n_groups = len(self.bwd_groups)
         sizes = [len(g) for g in reversed(self.bwd_groups)]
