@@ -73,6 +73,14 @@ extern thread_local int gdrn_tls_hip_error;
         }                                                    \
     } while (0)
 
+// one launch per element type of an entry point whose kernels are templates over float / the build's half; dtype without its flag bits
+#define DISPATCH(dtype, CALL_F32, CALL_BF16)                \
+    do {                                                    \
+        if ((dtype) == GDRN_DT_F32) { CALL_F32; }           \
+        else if ((dtype) == GDRN_DT_H16) { CALL_BF16; }    \
+        else return GDRN_ERR_ARG;                           \
+    } while (0)
+
 #ifdef GDRN_HALF_F16
 __device__ __forceinline__ float bf2f(bf16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
 // the low / high 16-bit element of a packed pair as fp32 (v_cvt_f32_f16, the high one through SDWA)
@@ -146,6 +154,8 @@ template <> __device__ __forceinline__ float ld1<bf16_t>(const bf16_t* p) { retu
 template <typename T> __device__ __forceinline__ void st1(T* p, float v);
 template <> __device__ __forceinline__ void st1<float>(float* p, float v) { *p = v; }
 template <> __device__ __forceinline__ void st1<bf16_t>(bf16_t* p, float v) { *p = f2bf(v); }
+
+__device__ __forceinline__ float sgn(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
 
 // sum over the 16 lanes of a DPP row (every lane gets the total): quad xor 1, quad xor 2, half-row mirror, row mirror
 __device__ __forceinline__ float row16_sum(float v) {

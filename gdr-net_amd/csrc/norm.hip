@@ -1004,12 +1004,6 @@ inline int ew_grid(long long n) { return (int)std::min<long long>((n + 255) / 25
 }  // namespace
 
 #define ST reinterpret_cast<hipStream_t>(stream)
-#define DISPATCH(dtype, CALL_F32, CALL_BF16)                \
-    do {                                                    \
-        if ((dtype) == GDRN_DT_F32) { CALL_F32; }           \
-        else if ((dtype) == GDRN_DT_H16) { CALL_BF16; }    \
-        else return GDRN_ERR_ARG;                           \
-    } while (0)
 
 extern "C" int gdrn_bn_finalize(const float* partial, int rows, int C, double count, const float* gamma, const float* beta,
                                 float* running_mean, float* running_var, long long* nbt, float momentum, float eps,

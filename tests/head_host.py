@@ -1,5 +1,5 @@
-"""Independent yardstick of the head-tail, map-loss and fused head-conv kernels (csrc/head_pose_loss.hip: head_tail_fwd*/bwd*, map_loss_fwd,
-head_conv_tail64, head_out_dgrad64 and the two finalizers): plain numpy restatements of each operation from its definition on [M][C] row-major
+"""Independent yardstick of the head-tail, map-loss and fused head-conv kernels (csrc/head_tail.hip: head_tail_fwd*/bwd*, map_loss_fwd and the two
+finalizers; csrc/head_conv.hip: head_conv_tail64, head_out_dgrad64): plain numpy restatements of each operation from its definition on [M][C] row-major
 arrays, M = N * HW pixels, no device code.  Operands enter as the values they have after storage (logits, coordinates, extents, targets and
 statistics fp32; pnp, d_pnp, x, w, dy, raw in the type under test).  Every function takes the dtype it computes in: np.float64 is the
 reference, np.float32 the "reference at the kernel's precision" whose distance from the fp64 run (e32) sizes the bounds of everything that goes

@@ -1,4 +1,4 @@
-"""fp64 yardstick of pose_loss_kernel (csrc/head_pose_loss.hip, entry point gdrn_pose_loss): the functions of oracle/gdrn_oracle.py
+"""fp64 yardstick of pose_loss_kernel (csrc/pose_loss.hip, entry point gdrn_pose_loss): the functions of oracle/gdrn_oracle.py
 (ortho6d_to_mat_batch, pose_decode_train, pose_decode_test, get_closest_rot_batch and the loss_PM_R / loss_centroid / loss_z lines of
 gdrn_loss) run in torch.float64 on the CPU on exactly the arrays gdrn_pose_params takes, their unit gradients by torch.autograd, and the
 same oracle once more in torch.float32: the "reference at the kernel's precision" whose distance from the fp64 run (e32) sizes the

@@ -1,4 +1,4 @@
-"""Per-element tests (-m gpu) of the head-tail, map-loss and fused head-conv kernels of csrc/head_pose_loss.hip at their launch edges, against the
+"""Per-element tests (-m gpu) of the head-tail, map-loss and fused head-conv kernels of csrc/head_tail.hip and csrc/head_conv.hip at their launch edges, against the
 fp64 yardstick of tests/head_host.py (pinned on the CPU by tests/test_head_host_cpu.py):
 
   (a) the 64-region kernels head_tail_fwd64<T, LOSS> / head_tail_bwd64 through gdrn_head_tail_fwd, gdrn_head_tail_loss_fwd (atomics and partial

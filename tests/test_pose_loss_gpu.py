@@ -1,4 +1,4 @@
-"""Per-element tests (-m gpu) of pose_loss_kernel (csrc/head_pose_loss.hip) through gdrn_pose_loss against the fp64 autograd reference of
+"""Per-element tests (-m gpu) of pose_loss_kernel (csrc/pose_loss.hip) through gdrn_pose_loss against the fp64 autograd reference of
 tests/pose_host.py (pinned on the CPU by tests/test_pose_host_cpu.py): the decode (train and test mode), the closest symmetric target, the
 three pose losses (atomics and per-RoI rows), all three planes of dL/dfc, the weighted 16-bit gradient and the fc tail, at N <= 8 and
 npts <= 700, every output pre-filled with NaN inside a guarded buffer.
