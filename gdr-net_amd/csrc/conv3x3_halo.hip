@@ -789,6 +789,9 @@ extern "C" int gdrn_conv3x3_halo(const gdrn_conv_params* pp, void* stream) {
         if ((unsigned long long)p.M * (unsigned long long)p.bnb_cs * 4ull >= (1ull << 32)) return GDRN_ERR_SHAPE;
     }
     if ((unsigned long long)p.M * (unsigned long long)std::max(p.y_cs, p.add_cs) * 4ull >= (1ull << 32)) return GDRN_ERR_SHAPE;  // 32-bit offsets
+    // ... and so are the patch offsets of the kernel (poff = pixel * x_cs * sizeof(T) + chunk; xf_x2 and xf_out are indexed with them too): with
+    // x_cs > y_cs (fp32), or x_cs > 2 * max(y_cs, add_cs) (16-bit), the line above does not cover them (gdrn_v3_launch has the same check)
+    if ((unsigned long long)p.M * (unsigned long long)p.x_cs * (unsigned long long)esz >= (1ull << 32)) return GDRN_ERR_SHAPE;
     if (p.dtype == GDRN_DT_F32 && (p.xf_mode || p.bnb_x)) return GDRN_ERR_ARG;   // transforms / fused BatchNorm-backward epilogue: 16-bit only
     if (p.xf_mode) {  // operand transform while staging
         if (p.xf_mode < 0 || p.xf_mode > 4 || !p.xf_c || p.Cin > XF_MAX_CIN || (p.Cin & 7)) return GDRN_ERR_ARG;

@@ -78,23 +78,28 @@ def pack_dgrad(w, dt, flip, rows_valid_pad=None, cout_p=None):
 
 
 def conv_gemm(x, w, B, Hi, Wi, Cin, x_cs, Ho, Wo, Cout, KH, KW, stride, pad, dt, mode=0, bias=None, addend=None, act=0,
-              out_f32=0, y_cs=None, want_stats=False, halo=False, bnb=None, xf=None, v3=False, reps=0):
+              out_f32=0, y_cs=None, want_stats=False, halo=False, bnb=None, xf=None, v3=False, reps=0,
+              y_buf=None, stats_buf=None, rows_buf=None, w_rows=None, halo_waves=None, prepacked=False, rc=False, info=None):
     """bnb (halo and generic kernel, bf16): dict(x, mask|None, mean, invstd, scale|None, shift|None) -> fused BatchNorm-backward statistics;
     the second return value is then the [tiles][2][Cout] rows buffer.
     xf (halo only): dict(mode, relu, x2, a, b, c, c2, msc, msh, out) device tensors -> operand transform while staging.
     v3 (with halo): True = the second-generation kernel (operand of gdrn_pack_wfrag32, w_frag = 2); 4 / 8 = the first kernel with
     gdrn_conv_params.halo_waves forced (the default, 0, lets the library pick by grid size: the small test grids get the eight-wave form).
-    reps > 0: also time `reps` back-to-back launches with HIP events; the average (ms) is returned as a third value."""
+    reps > 0: also time `reps` back-to-back launches with HIP events; the average (ms) is returned as a third value.
+    Optional, for tests/test_conv3x3_edges_gpu.py (the defaults are what every other caller gets): y_buf / stats_buf / rows_buf = the caller's
+    own (fenced) output, statistics and BatchNorm-backward rows tensors instead of fresh ones; w_rows / halo_waves = the values to put into
+    gdrn_conv_params whatever w and v3 say; prepacked = w is passed as it is; rc = return the entry point's status instead of raising on
+    it; info = a dict that receives the library's own answers for the launch (tile, halo_waves, stats_rows)."""
     lib = cabi.load(dt)
     waves = v3 if (v3 is not True and v3 in (4, 8)) else 0   # v3 = 4 / 8: first halo kernel, forced four- / eight-wave form (halo_waves)
     v3 = v3 is True
-    if halo:  # the halo kernels take a fragment-major permutation of the same operand
+    if halo and not prepacked:  # the halo kernels take a fragment-major permutation of the same operand
         wf = torch.empty_like(w)
         check((lib.gdrn_pack_wfrag32 if v3 else lib.gdrn_pack_wfrag)(ptr(w), ptr(wf), w.shape[0], Cin, dt, stream()), "pack_wfrag")
         w = wf
     y_cs = y_cs or ru(Cout, 4)
     ydt = torch.float32 if (out_f32 or dt == F32) else tdt(dt)
-    y = torch.full((B, Ho, Wo, y_cs), float("nan"), dtype=ydt, device=DEV)
+    y = y_buf if y_buf is not None else torch.full((B, Ho, Wo, y_cs), float("nan"), dtype=ydt, device=DEV)
     cp = ConvParams()
     cp.x, cp.w, cp.y = ptr(x), ptr(w), ptr(y)
     cp.bias, cp.addend = ptr(bias), ptr(addend)
@@ -104,9 +109,9 @@ def conv_gemm(x, w, B, Hi, Wi, Cin, x_cs, Ho, Wo, Cout, KH, KW, stride, pad, dt,
     cp.KH, cp.KW, cp.stride, cp.pad = KH, KW, stride, pad
     cp.mode, cp.act, cp.out_f32 = mode, act, out_f32
     cp.M = B * (Ho // 2) * (Wo // 2) if mode == 1 else B * Ho * Wo
-    cp.w_rows, cp.dtype = w.shape[0], dt
+    cp.w_rows, cp.dtype = (w.shape[0] if w_rows is None else w_rows), dt
     cp.w_frag = 2 if (halo and v3) else 0
-    cp.halo_waves = waves if halo else 0
+    cp.halo_waves = (waves if halo else 0) if halo_waves is None else halo_waves
     cp.v3_min_wg = 1   # the 256-channel tile of the second-generation kernel also on the small grids of these tests
     # (every operand goes in before the tile / statistics-row queries: the second-generation kernel's tile depends on them)
     if bnb is not None:
@@ -118,16 +123,25 @@ def conv_gemm(x, w, B, Hi, Wi, Cin, x_cs, Ho, Wo, Cout, KH, KW, stride, pad, dt,
     stats = None
     if want_stats:
         rows = (lib.gdrn_conv3x3_stats_rows if halo else lib.gdrn_conv_stats_rows)(C.byref(cp))
-        stats = torch.zeros(rows, 2, Cout, dtype=torch.float32, device=DEV)
+        stats = stats_buf if stats_buf is not None else torch.zeros(rows, 2, Cout, dtype=torch.float32, device=DEV)
         cp.stats = ptr(stats)
     if bnb is not None:
         nrows = (lib.gdrn_conv3x3_stats_rows if halo else lib.gdrn_conv_stats_rows)(C.byref(cp))
-        rows_t = torch.full((nrows, 2, Cout), float("nan"), dtype=torch.float32, device=DEV)
+        rows_t = rows_buf if rows_buf is not None else torch.full((nrows, 2, Cout), float("nan"), dtype=torch.float32, device=DEV)
         cp.bnb_x, cp.bnb_mask, cp.bnb_cs = ptr(bnb["x"]), ptr(bnb.get("mask")), bnb["x"].shape[-1]
         cp.bnb_mean, cp.bnb_invstd, cp.bnb_scale, cp.bnb_shift = ptr(bnb["mean"]), ptr(bnb["invstd"]), ptr(bnb.get("scale")), ptr(bnb.get("shift"))
         cp.bnb_rows = ptr(rows_t)
         stats = rows_t  # per-tile rows [nrows][2][Cout]: callers sum over dim 0
     fn = lib.gdrn_conv3x3_halo if halo else lib.gdrn_conv_gemm
+    if info is not None and halo:
+        th, tw, bn = C.c_int(0), C.c_int(0), C.c_int(0)
+        lib.gdrn_conv3x3_tile(C.byref(cp), C.byref(th), C.byref(tw), C.byref(bn))
+        info.update(tile=(th.value, tw.value, bn.value), halo_waves=lib.gdrn_conv3x3_halo_waves(C.byref(cp)),
+                    stats_rows=lib.gdrn_conv3x3_stats_rows(C.byref(cp)))
+    if rc:
+        status = fn(C.byref(cp), stream())
+        torch.cuda.synchronize()
+        return status
     check(fn(C.byref(cp), stream()), "conv")
     torch.cuda.synchronize()
     if reps > 0:
@@ -253,3 +267,38 @@ class Guarded:
         tail = self.buf[self.n:]
         assert bool((tail == 255).all() if tail.dtype == torch.uint8 else torch.isnan(tail).all()), f"{what}: written past its end"
         return self.t.cpu().numpy() if self.t.dtype == torch.uint8 else to_host(self.t)
+
+
+# ---------------------------------------------------------------------------------------------- helpers of tests/test_conv3x3_edges_gpu.py
+FENCE = {torch.int16: 0x7FB5, torch.int32: 0x7FB5A5A5}   # a NaN with a payload in bf16, fp16 and fp32: a guard must come back bit for bit
+
+
+class Fenced:
+    """a [rows][cs] tensor of `dtype` with `guard` rows in front of it and behind it; the guard rows and the pad columns >= C hold FENCE, the
+    interior NaN.  check(): every fence element is still the same bits; host(): the interior [rows][C] in fp64 (after check())."""
+
+    def __init__(self, rows, cs, C_, dtype, guard=2):
+        it = torch.int32 if dtype == torch.float32 else torch.int16
+        self.rows, self.cs, self.C, self.guard, self.pat = rows, cs, C_, guard, FENCE[it]
+        self.raw = torch.full(((rows + 2 * guard), cs), self.pat, dtype=it, device=DEV)
+        self.all = self.raw.view(dtype)
+        self.t = self.all[guard:guard + rows]
+        self.t[:, :C_] = float("nan")
+
+    def check(self, what="output"):
+        torch.cuda.synchronize()
+        g = self.guard
+        r = self.raw.cpu().numpy()
+        assert (r[:g] == self.pat).all(), f"{what}: written in front of its first row"
+        assert (r[g + self.rows:] == self.pat).all(), f"{what}: written behind its last row"
+        assert (r[g:g + self.rows, self.C:] == self.pat).all(), f"{what}: pad columns written"
+
+    def host(self, what="output"):
+        self.check(what)
+        return to_host(self.t[:, :self.C])
+
+    def untouched(self):
+        torch.cuda.synchronize()
+        g = self.guard   # (on the device: the refusal tests hold buffers of 256 MB)
+        fence = (self.raw[:g] == self.pat).all() & (self.raw[g + self.rows:] == self.pat).all() & (self.raw[:, self.C:] == self.pat).all()
+        return bool(fence) and bool(torch.isnan(self.t[:, :self.C]).all())
