@@ -267,6 +267,11 @@ _SIGS = {
     "gdrn_mssd_mspd_workspace_bytes": [I, I, I],
     "gdrn_mssd_mspd": [P, P, P, P, P, P, P, I, P, P, I, P, P, P, I, I, P, P, P],
     "gdrn_bop_recall_accumulate": [P, I, P, P, P, I, P, I, D, P, P, P, P, P, P, P, P],
+    "gdrn_ad_errors_workspace_bytes": [I, I],
+    "gdrn_ad_errors": [P, P, P, P, P, P, I, P, P, I, I, P, P, P],
+    "gdrn_sym_errors_workspace_bytes": [I, I, I],
+    "gdrn_sym_errors": [P, P, P, P, P, P, P, I, P, P, I, P, P, P, I, I, P, P, P],
+    "gdrn_score_recall_accumulate": [P, P, P, P, I, P, P, I, P, P, P],
     "gdrn_aug_mask_cuts": [P, C.POINTER(AugTask), I, P, P],
     "gdrn_aug_frames": [P, C.POINTER(AugTask), I, P, LL, P, P],
     "gdrn_rle_decode": [P, C.POINTER(RleTask), I, P, LL, P, LL, P, P, P],
@@ -286,7 +291,8 @@ _SIGS = {
 
 _SIGS["gdrn_half_format"] = []
 _RET_LL = ("gdrn_workspace_bytes", "gdrn_pose_metrics_workspace_bytes", "gdrn_pnp_workspace_bytes", "gdrn_vsd_workspace_bytes",
-           "gdrn_mssd_mspd_workspace_bytes", "gdrn_model_prep_workspace_bytes")
+           "gdrn_mssd_mspd_workspace_bytes", "gdrn_model_prep_workspace_bytes", "gdrn_ad_errors_workspace_bytes",
+           "gdrn_sym_errors_workspace_bytes")
 EXPORTS = tuple(_SIGS.keys())
 _libs = {}
 

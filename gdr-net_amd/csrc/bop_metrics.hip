@@ -14,6 +14,7 @@
 // operation is an explicit fma().  (No 16-bit code: both library builds compile the same thing.)
 #include "common.h"
 #include "geom64.h"
+#include "points64.h"
 #include "dist64.h"
 #include "../../include/gdrn_hip.h"
 
@@ -29,26 +30,7 @@ constexpr int VSD_MAX_T = GDRN_VSD_MAX_TAUS;
 constexpr int MS_SLAB = 8;                           // symmetry transformations per workgroup
 constexpr int NTH = GDRN_BOP_NTH;
 
-// misc.project_pts (misc.py:511-525): P = K [R | t] (3 x 4), then P [p, 1] divided by its third row
-__device__ __forceinline__ void make_proj(const double* K, const double* R, const double* t, double* P) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) P[r * 4 + q] = fma(K[r * 3 + 0], R[q], fma(K[r * 3 + 1], R[3 + q], K[r * 3 + 2] * R[6 + q]));
-        P[r * 4 + 3] = fma(K[r * 3 + 0], t[0], fma(K[r * 3 + 1], t[1], K[r * 3 + 2] * t[2]));
-    }
-}
-__device__ __forceinline__ void project(const double* P, V3 p, double& u, double& v) {
-    const double a = fma(P[0], p.x, fma(P[1], p.y, fma(P[2], p.z, P[3])));
-    const double b = fma(P[4], p.x, fma(P[5], p.y, fma(P[6], p.z, P[7])));
-    const double w = fma(P[8], p.x, fma(P[9], p.y, fma(P[10], p.z, P[11])));
-    u = a / w;
-    v = b / w;
-}
-
-// maximum / minimum that keep a NaN once they have seen one (fmax / fmin drop it): a NaN pose gives a NaN error
-__device__ __forceinline__ double nanmax(double m, double d) { return (d > m || d != d) ? d : m; }
-__device__ __forceinline__ double nanmin(double m, double d) { return (d < m || d != d) ? d : m; }
+// (misc.project_pts as make_proj / project, the pose of a symmetry under the ground truth and the NaN-keeping nanmax / nanmin: points64.h)
 
 __device__ __forceinline__ double wave_nanmax(double v) {
 #pragma unroll
@@ -206,12 +188,7 @@ __global__ __launch_bounds__(BM_THREADS) void ms_est_kernel(const double* __rest
 // the pose of symmetry k of the class under the ground truth: R_gt S_k, R_gt t_k + t_gt (pose_error.py:149-150), and its projection matrix
 __device__ __forceinline__ void sym_pose(const double* Rg, const double* tg, const double* K, const double* S, const double* ts, double* R, double* t,
                                          double* P) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) R[r * 3 + q] = fma(Rg[r * 3 + 0], S[q], fma(Rg[r * 3 + 1], S[3 + q], Rg[r * 3 + 2] * S[6 + q]));
-        t[r] = fma(Rg[r * 3 + 0], ts[0], fma(Rg[r * 3 + 1], ts[1], Rg[r * 3 + 2] * ts[2])) + tg[r];
-    }
+    sym_gt_pose(Rg, tg, S, ts, R, t);
     make_proj(K, R, t, P);
 }
 

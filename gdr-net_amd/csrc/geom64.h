@@ -1,4 +1,4 @@
-// What the fp64 evaluation kernels (pose_metrics.hip, bop_metrics.hip, render.hip, pnp.hip) share: the posed point and the fixed-order sums.
+// What the fp64 evaluation kernels (pose_metrics.hip, bop_metrics.hip, sixd_scores.hip, render.hip, pnp.hip) share: the posed point and the fixed-order sums.
 // Include after common.h.  render.hip and bop_metrics.hip switch floating-point contraction OFF behind their includes, the other two leave it on:
 // everything here is explicit fma() and plain additions only, so it is the same operation sequence on both sides of that pragma.
 #pragma once

@@ -10,6 +10,7 @@
 // two runs give the same bits.  (The file has no 16-bit code: both library builds compile the same thing.)
 #include "common.h"
 #include "geom64.h"
+#include "points64.h"
 #include "../../include/gdrn_hip.h"
 
 namespace {
@@ -20,15 +21,7 @@ constexpr int PM_SLAB = PM_THREADS * PM_G;     // points of one workgroup
 constexpr int PM_TILE = 512;                   // estimate-posed points per LDS tile (3 x 4 KiB)
 constexpr int PM_FLAGS = 15;
 
-// pose_error.py:400-415: rad2deg(arccos(clamp(0.5 (min(tr(A B^T), 3) - 1), -1, 1)))
-__device__ __forceinline__ double re_deg(const double* A, const double* B) {
-    double tr = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) tr += A[i] * B[i];
-    tr = tr <= 3.0 ? tr : 3.0;
-    const double c = fmin(1.0, fmax(-1.0, 0.5 * (tr - 1.0)));
-    return acos(c) * (180.0 / 3.14159265358979323846);
-}
+// (re_deg, pose_error.py:400-415, and the adi tile loop: points64.h)
 
 // One thread per row: te, the closest ground-truth rotation (kept in rsel[row][9] for the point kernel) and re.
 __global__ __launch_bounds__(PM_THREADS) void pose_row_kernel(const double* __restrict__ R_est, const double* __restrict__ t_est,
@@ -71,7 +64,7 @@ __global__ __launch_bounds__(PM_THREADS) void pose_row_kernel(const double* __re
         }
     }
     e[1] = best;
-    e[2] = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+    e[2] = norm3(d0, d1, d2);
 #pragma unroll
     for (int k = 0; k < 9; ++k) rsel[(size_t)i * 9 + k] = Rb[k];
 }
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(PM_THREADS) void pose_points_kernel(const double* _
             s_pr += sqrt(du * du + dv * dv);
             if (!symc) {
                 const double dx = pe.x - g[u].x, dy = pe.y - g[u].y, dz = pe.z - g[u].z;
-                s_ad += sqrt(dx * dx + dy * dy + dz * dz);
+                s_ad += norm3(dx, dy, dz);
             }
         }
     }
@@ -138,26 +131,7 @@ __global__ __launch_bounds__(PM_THREADS) void pose_points_kernel(const double* _
         double best[PM_G];
 #pragma unroll
         for (int u = 0; u < PM_G; ++u) best[u] = INFINITY;
-        for (int t0 = 0; t0 < n; t0 += PM_TILE) {
-            const int cnt = min(PM_TILE, n - t0);
-            __syncthreads();   // the previous tile has been consumed
-            for (int j = tid; j < cnt; j += PM_THREADS) {
-                const V3 pe = xform(Re, te, load3(P + (size_t)(t0 + j) * 3));
-                sx[j] = pe.x;
-                sy[j] = pe.y;
-                sz[j] = pe.z;
-            }
-            __syncthreads();
-#pragma unroll 4
-            for (int j = 0; j < cnt; ++j) {
-                const double ex = sx[j], ey = sy[j], ez = sz[j];
-#pragma unroll
-                for (int u = 0; u < PM_G; ++u) {
-                    const double dx = g[u].x - ex, dy = g[u].y - ey, dz = g[u].z - ez;
-                    best[u] = fmin(best[u], dx * dx + dy * dy + dz * dz);
-                }
-            }
-        }
+        nearest_sq_tiles<PM_G, PM_TILE, PM_THREADS>(P, n, Re, te, g, best, sx, sy, sz, tid);
 #pragma unroll
         for (int u = 0; u < PM_G; ++u)
             if (valid[u]) s_ad += sqrt(best[u]);

@@ -736,6 +736,28 @@ def bop_test_depth(inp, depth_gt):
 
 
 # ----------------------------------------------------------------------------------------------
+# estimates of the YCB-V score tables (gdrnet_amd.sixd_scores, golden G18)
+# ----------------------------------------------------------------------------------------------
+SIXD_SCORE_SEEDS = {"sym": 191}
+# ^ the seed golden G18 was drawn with (tests/golden/make_golden_g18.py moves on while an error of the reference, normalised as its score script
+#   normalises it, sits within 1e-6 relative of one of its thresholds)
+SIXD_SYM_CLASSES = (0, 1)   # the classes whose "ad" is adi (the fixture's dp_model["symmetric_obj_ids"]); classes 2 (the single point) and 3 (8195 points) take add
+
+
+def make_sixd_score_inputs(case="sym", seed=None):
+    """Inputs of the score golden G18 (gdrnet_amd.sixd_scores against lib/pysixd/pose_error.py add / adi / re_sym / te_sym / arp_2d_sym and the
+    toolkit's matching and recall), fp64, metres: the rows of ``make_bop_metric_inputs("sym")`` drawn with this fixture's own seed -- 41 estimates
+    graded from exact to far over four classes (1031 points x 314 transformations | 257 x 3 with translation parts | ONE point, identity only |
+    8195 x 314), rows 0 and 6 with est = gt, rows 5 and 8 with est = gt o S_k, every fourth estimate of a symmetric class near another member of
+    its set, 3 targets without an estimate -- plus ``sym_classes``, the classes scored with adi under "ad"."""
+    if case != "sym":
+        raise ValueError(case)
+    inp = make_bop_metric_inputs("sym", seed=SIXD_SCORE_SEEDS[case] if seed is None else seed)
+    inp["sym_classes"] = SIXD_SYM_CLASSES
+    return inp
+
+
+# ----------------------------------------------------------------------------------------------
 # vertex clouds of the model preparation (gdrnet_amd.model_prep, golden G16)
 # ----------------------------------------------------------------------------------------------
 MODEL_PREP_SEED = 161

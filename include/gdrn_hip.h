@@ -857,6 +857,52 @@ int gdrn_bop_recall_accumulate(const double* vsd_err, int T, const double* mssd_
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The errors and recall counts of the reference's YCB-V tables (added within ABI 5: new entry points, nothing changed): the error types
+ * AUCadd / AUCadi / AUCad, ABSadd / ABSadi / ABSad, add, adi, reS, teS, reteS and projS of lib/pysixd/scripts/eval_pose_results_more.py:64-93, which
+ * the reference scores on the host from a CSV (eval_calc_errors.py:395-448, pose_error.py:184-234,297-337, eval_calc_scores.py, pose_matching.py).
+ * Everything is fp64, lengths in metres; poses, K, labels / labels_host and the per-class tables pts / npts / sym_R / sym_t / nsym as in
+ * gdrn_pose_errors and gdrn_mssd_mspd (labels_host is checked against [0, C) on the host before anything is launched: GDRN_ERR_ARG; rows beyond
+ * npts[c] and transformations beyond nsym[c] never enter a result).  No floating-point atomics, sums and minima in a fixed order: the same call
+ * gives the same bits, and a row's result does not depend on the other rows of the call.  N <= 65535 per call (GDRN_ERR_SHAPE).
+ *
+ * gdrn_ad_errors: err [N][2] = (add, adi) of EVERY row whatever its class, both against the plain ground-truth pose: add the mean distance of
+ *   corresponding points, adi the mean distance from each ground-truth-posed point to the nearest estimate-posed point (exact, brute force; the
+ *   loop of gdrn_pose_errors).  Work is spread over (row, slab of GDRN_SIXD_AD_SLAB points), the estimate-posed points pass through LDS in tiles of
+ *   GDRN_SIXD_AD_TILE; the slabs' sums are added in slab order.  workspace: gdrn_ad_errors_workspace_bytes(N, n_max) bytes, no initialisation.
+ *
+ * gdrn_sym_errors: err [N][3] = (re_sym [deg], te_sym [m], arp_2d_sym [px]), each the minimum over the class's nsym[c] >= 1 transformations
+ *   (R_gt S, R_gt t_S + t_gt) of: the rotation error to R_est | pose_error.te_sym AS IT RUNS (below) | the mean over the class's points of the
+ *   distance in the image between the point under that pose and under the estimate (K [R | t] [p, 1] divided by its third row).
+ *   te_sym: pose_error.py:218 adds the flattened t_gt [3] to the column R_gt t_S [3,1]; numpy broadcasts, and the value returned is the Frobenius
+ *   norm of M[i][j] = (R_gt t_S)[i] + t_gt[j] - t_est[j], i.e. sqrt(3 |a|^2 + 3 |d|^2 + 2 sum(a) sum(d)) with a = R_gt t_S, d = t_gt - t_est --
+ *   sqrt(3) |d| for a class with the identity only, not |d|.  The toolkit's teS / reteS decisions are taken on it, so this is the value computed;
+ *   the plain translation error is err[2] of gdrn_pose_errors.  nsym[c] = 0 gives NaN; a NaN in
+ *   t_est, t_gt or K gives NaN in te_sym / arp_2d_sym.  Work is spread over (row, slab of GDRN_SIXD_SYM_SLAB transformations), the slabs' minima
+ *   are finished in slab order.  workspace: gdrn_sym_errors_workspace_bytes(N, n_max, S_max) bytes, no initialisation.
+ *
+ * gdrn_score_recall_accumulate: adds a batch (ad_err [N][2] from gdrn_ad_errors, sym_err [N][3] from gdrn_sym_errors) to the caller's per-class
+ *   state (device memory, zeroed by the caller before the first call); diameter [C] fp64, ad_is_adi [C] int32 (non-zero: "ad" is adi for the class,
+ *   dp_model["symmetric_obj_ids"]).  hits [C][GDRN_SIXD_NFLAGS] += the strict-< decisions (pose_matching.py:68), cm = 100 m:
+ *     [0..9] AUCadd: add cm < 1..10 | [10..19] AUCadi: adi | [20..29] AUCad: ad | [30] ABSadd: add cm < 2 | [31] ABSadi | [32] ABSad |
+ *     [33..35] add / diameter < 0.02, 0.05, 0.1 | [36..38] adi / diameter | [39..41] reS: re_sym < 2, 5, 10 | [42..44] teS: te_sym cm < 2, 5, 10 |
+ *     [45..47] reteS: both at once | [48..50] projS: arp_2d_sym < 2, 5, 10
+ *   (eval_calc_scores.py:238-250 divides add and adi by the diameter and nothing else of these);  seen [C] += rows of the class.  One workgroup
+ *   per class, integer adds; calls on one stream follow each other. */
+#define GDRN_SIXD_AD_SLAB 1024
+#define GDRN_SIXD_AD_TILE 512
+#define GDRN_SIXD_SYM_SLAB 8
+#define GDRN_SIXD_NFLAGS 51
+long long gdrn_ad_errors_workspace_bytes(int N, int n_max);
+int gdrn_ad_errors(const double* R_est, const double* t_est, const double* R_gt, const double* t_gt, const int* labels, const int* labels_host,
+                   int N, const double* pts, const int* npts, int n_max, int C, double* err, void* workspace, void* stream);
+long long gdrn_sym_errors_workspace_bytes(int N, int n_max, int S_max);
+int gdrn_sym_errors(const double* R_est, const double* t_est, const double* R_gt, const double* t_gt, const double* K, const int* labels,
+                    const int* labels_host, int N, const double* pts, const int* npts, int n_max, const double* sym_R, const double* sym_t,
+                    const int* nsym, int S_max, int C, double* err, void* workspace, void* stream);
+int gdrn_score_recall_accumulate(const double* ad_err, const double* sym_err, const int* labels, const int* labels_host, int N,
+                                 const double* diameter, const int* ad_is_adi, int C, long long* hits, long long* seen, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Background replacement and colour augmentation of whole training frames (added within ABI 5: new entry points, nothing changed): what the
  * reference does per sample on the host between decoding and cropping -- replace_bg / get_bg_image (core/base_data_loader.py:320-403,
  * resize_short_edge core/utils/data_utils.py:161-187) and the imgaug chain of INPUT.COLOR_AUG_CODE (core/gdrn_modeling/data_loader.py:319-343) --
