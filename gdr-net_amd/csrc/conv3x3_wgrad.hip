@@ -374,6 +374,15 @@ extern "C" int gdrn_conv3x3_wgrad_ok(const gdrn_wgrad_params* p) {
           (p->x_cs % 8) == 0 && (p->dy_cs % 8) == 0 && (p->Wo % 8) == 0))
         return 0;
     if (p->variant != 0) return 0;   // (GDRN_WGRAD_W128, the 128 x 64 tile of rounds 4-5, is gone: r6)
+    // (0 passes every `% n == 0` above: an empty map divides by zero in the launcher, an empty channel count gives a kernel no tile)
+    if (p->Cin <= 0 || p->Cout <= 0 || p->Ho <= 0 || p->Wo <= 0 || p->x_cs < p->Cin || p->dy_cs < p->Cout) return 0;
+    // wgrad_tile forms its byte offsets into dy (pixel * dy_cs * 2) and x (pixel * x_cs * 2 + granule) in 32 bits: M pixels of dy and the
+    // M / (Ho Wo) images of x must each end below 2^32 bytes (M <= 0 or no multiple of Ho Wo: the launcher's own refusal)
+    if (p->M > 0) {
+        const unsigned long long nimg = ((unsigned long long)p->M + (unsigned long long)p->Ho * p->Wo - 1) / ((unsigned long long)p->Ho * p->Wo);
+        if ((unsigned long long)p->M * (unsigned long long)p->dy_cs * 2ull >= (1ull << 32)) return 0;
+        if (nimg * (unsigned long long)p->Hi * (unsigned long long)p->Wi * (unsigned long long)p->x_cs * 2ull >= (1ull << 32)) return 0;
+    }
     if (p->stride == 1) return p->Hi == p->Ho && p->Wi == p->Wo && (p->Ho % 8) == 0;
     if (p->stride == 2) return p->Hi == 2 * p->Ho && p->Wi == 2 * p->Wo && (p->Ho % 4) == 0;
     return 0;

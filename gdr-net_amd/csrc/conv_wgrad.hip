@@ -241,7 +241,11 @@ extern "C" int gdrn_conv_wgrad(const gdrn_wgrad_params* pp, void* stream) {
     if (p.dtype != GDRN_DT_F32 && p.dtype != GDRN_DT_H16) return GDRN_ERR_ARG;
     const int esz = p.dtype == GDRN_DT_H16 ? 2 : 4;
     if (p.Cin <= 0 || p.Cin % 64 != 0 || p.M <= 0 || p.Cout <= 0) return GDRN_ERR_SHAPE;
-    if ((p.x_cs * esz) % 16 != 0 && (p.x_cs * esz) % 8 != 0) return GDRN_ERR_SHAPE;
+    // the kernel divides by Ho * Wo and walks KH * KW taps: an empty map, tap set or stride is no shape (pixel -> (n, oy, ox) would index x with garbage)
+    if (p.KH <= 0 || p.KW <= 0 || p.stride <= 0 || p.pad < 0 || p.Hi <= 0 || p.Wi <= 0 || p.Ho <= 0 || p.Wo <= 0) return GDRN_ERR_SHAPE;
+    if (p.M % (p.Ho * p.Wo) != 0) return GDRN_ERR_SHAPE;   // whole images: the image index of pixel m is m / (Ho Wo)
+    if (p.x_cs <= 0 || ((p.x_cs * esz) % 16 != 0 && (p.x_cs * esz) % 8 != 0)) return GDRN_ERR_SHAPE;
+    if ((p.dy_cs * esz) % 16 != 0) return GDRN_ERR_SHAPE;  // dY rows are read as 16-byte granules
     const int bco = p.Cout <= 64 ? 64 : 128;
     const int bci = (p.Cin % 128 == 0) ? 128 : 64;
     // dY rows are read in BCO-wide slabs: the caller guarantees dy_cs >= ceil(Cout/BCO)*BCO readable columns

@@ -232,6 +232,11 @@ int gdrn_conv3x3_halo_waves(const gdrn_conv_params* p);
  *   sum_m dy[m][co] * x[pix(m,tap)][ci]  (mode-0 gather; bf16 fragments through the LDS transpose read).  variant: 0 (only gdrn_conv3x3_wgrad* read it, see GDRN_WGRAD_W128).
  *   splits <= 0: automatic pixel-range split.
  * ws (gdrn_conv3x3_wgrad only, else NULL): per-split partial tiles go here (plain stores) instead of atomics on dw.
+ * gdrn_conv_wgrad: Cin a multiple of 64; Cout <= 64 reads dy in 64-column slabs, else in 128-column slabs: dy_cs >= Cout rounded up to the
+ *   slab, dy_cs * sizeof(T) a multiple of 16, x_cs * sizeof(T) a multiple of 8; x_cs < Cin is the window form ("channel" c of pixel (iy, ix) =
+ *   element c of the flat row that starts there: the caller keeps every window inside its buffer).  Refused with GDRN_ERR_SHAPE: KH, KW, stride,
+ *   Hi, Wi, Ho, Wo <= 0, pad < 0, M <= 0 or no multiple of Ho * Wo (whole images), the strides above; GDRN_ERR_ARG: x, dy or dw NULL, a dtype
+ *   other than GDRN_DT_F32 / GDRN_DT_H16.  Rows co >= Cout of dw are never written.
  * Replaces the autograd weight-gradients of the same layers (engine.py:279). */
 typedef struct gdrn_wgrad_params {
     const void* x;
@@ -248,7 +253,10 @@ int gdrn_conv_wgrad(const gdrn_wgrad_params* p, void* stream);
  * Wi = 2*Wo, Ho a multiple of 4, Wo of 8: the ResNet stage-entry convs, Patch-PnP's convs, and ConvTranspose2d(3, 2, 1, 1) with x = the
  * gradient of its output and dy = its input): a workgroup
  * accumulates a 64 x 64 (co x ci) tile of all nine taps from one staged 8x8 pixel patch per stage.  Same dw layout and
- * accumulate-with-atomics contract.  gdrn_conv3x3_wgrad_ok returns 1 when the shape is covered.
+ * accumulate-with-atomics contract.  gdrn_conv3x3_wgrad_ok returns 1 when the shape is covered; beyond the above it wants Cin, Cout, Ho,
+ * Wo > 0, x_cs >= Cin, dy_cs >= Cout, x_cs and dy_cs multiples of 8, variant 0, and -- the kernel forms its byte offsets into x and dy in 32
+ * bits -- M * dy_cs * 2 < 2^32 and (M / (Ho * Wo)) * Hi * Wi * x_cs * 2 < 2^32.  gdrn_conv3x3_wgrad returns GDRN_ERR_SHAPE for a shape that is
+ * not covered or an M that is <= 0 or no multiple of Ho * Wo, GDRN_ERR_ARG for x or dy NULL or dw and ws both NULL; nothing is written then.
  * With p->ws != NULL the partial tiles of the gdrn_conv3x3_wgrad_splits(p) pixel-range splits are stored to
  * ws[split][Cout*Cin*9] (fragment order, no atomics, dw unused) and gdrn_wgrad_reduce_multi sums them for a whole
  * table of layers in one launch, writing dst[co*s_co + ci*s_ci + tap*s_t] (e.g. the OIHW .grad: s_co = Cin*9, s_ci = 9,
@@ -257,7 +265,9 @@ int gdrn_conv3x3_wgrad(const gdrn_wgrad_params* p, void* stream);
 int gdrn_conv3x3_wgrad_ok(const gdrn_wgrad_params* p);
 int gdrn_conv3x3_wgrad_splits(const gdrn_wgrad_params* p);
 /* Grouped launch: the weight gradients of ntasks layers in one grid.  tasks_dev: device array of gdrn_wgrad_params with
- * ws != NULL and splits = gdrn_conv3x3_wgrad_splits() of an explicit request (no empty split);
+ * ws != NULL and splits = gdrn_conv3x3_wgrad_splits() of an explicit request (no empty split).  The entry point cannot read its device
+ * table: every task must have passed gdrn_conv3x3_wgrad_ok and the M check of gdrn_conv3x3_wgrad on the host (the 32-bit offset limits
+ * included).  lds_bytes above 160 KiB: GDRN_ERR_ARG;
  * blk_start[i] = sum_{j<i} (Cout_j/64)*(Cin_j/64)*splits_j, nblocks = blk_start[ntasks]. */
 int gdrn_conv3x3_wgrad_multi(const gdrn_wgrad_params* tasks_dev, const int* blk_start_dev, int ntasks, int nblocks, void* stream);
 /* the same with an LDS request of lds_bytes (> 64 KiB: one workgroup per CU, the rest of the CU stays free for another stream's kernels) */

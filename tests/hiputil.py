@@ -302,3 +302,55 @@ class Fenced:
         g = self.guard   # (on the device: the refusal tests hold buffers of 256 MB)
         fence = (self.raw[:g] == self.pat).all() & (self.raw[g + self.rows:] == self.pat).all() & (self.raw[:, self.C:] == self.pat).all()
         return bool(fence) and bool(torch.isnan(self.t[:, :self.C]).all())
+
+
+# ---------------------------------------------------------------------------------------------- helpers of tests/test_wgrad_edges_gpu.py
+def wgrad_params(x, dy, dw, ws, Hi, Wi, Cin, x_cs, Ho, Wo, Cout, dy_cs, KH, KW, stride, pad, M, dt, splits=0, variant=0):
+    """gdrn_wgrad_params of tensors (or None) -- nothing is checked here: the refusal tests pass shapes the library must turn down"""
+    wp = WgradParams()
+    wp.x, wp.dy, wp.dw, wp.ws = ptr(x), ptr(dy), ptr(dw), ptr(ws)
+    wp.Hi, wp.Wi, wp.Cin, wp.x_cs = Hi, Wi, Cin, x_cs
+    wp.Ho, wp.Wo, wp.Cout, wp.dy_cs = Ho, Wo, Cout, dy_cs
+    wp.KH, wp.KW, wp.stride, wp.pad = KH, KW, stride, pad
+    wp.M, wp.dtype, wp.splits, wp.variant = M, dt, splits, variant
+    return wp
+
+
+def fenced_flat(n, row=1024):
+    """n fp32 elements (a multiple of `row`) as a Fenced buffer of rows of `row`: workspace slabs and flat gradients"""
+    assert n % row == 0
+    return Fenced(n // row, row, row, torch.float32)
+
+
+def same_bits(a, b):
+    """two fp32 device tensors hold the same bit patterns (NaN payloads included)"""
+    return bool(torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)))
+
+
+def wgrad_reduce(lib, tasks):
+    """gdrn_wgrad_reduce_multi on a table of dict(ws, dst, nsplit, Cout, Cin, cin_valid, s_co, s_ci, s_t) (ws, dst: tensors); the status"""
+    from gdrnet_amd.cabi import WreduceTask, to_device_table
+
+    tab = to_device_table([WreduceTask(ws=ptr(t["ws"]), dst=ptr(t["dst"]), nsplit=t["nsplit"], Cout=t["Cout"], Cin=t["Cin"], cin_valid=t["cin_valid"],
+                                       s_co=t["s_co"], s_ci=t["s_ci"], s_t=t["s_t"]) for t in tasks], DEV)
+    starts = [0]
+    for t in tasks:
+        starts.append(starts[-1] + t["Cout"] * t["Cin"] // 256)
+    stt = torch.tensor(starts, dtype=torch.int32, device=DEV)
+    rc = lib.gdrn_wgrad_reduce_multi(ptr(tab), ptr(stt), len(tasks), starts[-1], stream())
+    torch.cuda.synchronize()
+    return rc
+
+
+def fill(f, value=1.0):
+    """give the interior of a Fenced buffer a finite value: an atomic add onto NaN leaves NaN, so `untouched()` cannot see it"""
+    f.t[:, :f.C] = value
+    return f
+
+
+def holds(f, value=1.0):
+    """the fences of a Fenced buffer are intact and its interior still holds `value` everywhere"""
+    torch.cuda.synchronize()
+    g = f.guard
+    fence = (f.raw[:g] == f.pat).all() & (f.raw[g + f.rows:] == f.pat).all() & (f.raw[:, f.C:] == f.pat).all()
+    return bool(fence) and bool((f.t[:, :f.C] == value).all())
