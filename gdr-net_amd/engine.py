@@ -121,12 +121,9 @@ class Engine:
         # the head's BatchNorm + ReLU in front of an upsampling evaluated by the upsampling launch, its backward sums by the upsampling's adjoint
         # (r6, gdrn_bn_relu_upsample2x_fwd / gdrn_upsample2x_bwd_bnsums): "0" = separate launches (A/B, the bit-equality test)
         self.fuse_up = self.h16 and _os.environ.get("GDRN_FUSE_UP", "1") != "0"
-        # eval mode: a 64-channel BasicBlock (layer1) as one launch, its intermediate in LDS (r6, gdrn_block64_eval); "0" = two halo launches
-        self.block64 = self.h16 and _os.environ.get("GDRN_BLOCK64", "1") != "0"
-        # the stride-2 3x3 convs' forward pass (stage-entry conv1 + its 1x1 shortcut in one launch, Patch-PnP's convs) on the parity-plane halo
-        # kernel (r6, gdrn_conv3x3s2) where it covers the shape; "0" = the generic gather kernel
-        self.s2_halo = self.h16 and _os.environ.get("GDRN_S2_HALO", "1") != "0"
-        self.s2_tw8 = _os.environ.get("GDRN_S2_TW8", "1") != "0"   # 8-wide maps on the stride-2 kernels (two images per tile); 0: the generic kernel there (A/B)
+        # (settled in r6, switches gone: the 16-bit modes run a 64-channel BasicBlock in eval mode as one launch, gdrn_block64_eval, and the 3x3
+        # stride-2 convs and the head's ConvTranspose on the parity-plane / parity-class kernels, gdrn_conv3x3s2 / gdrn_conv3x3s2_dgrad, 8-wide maps
+        # included, wherever the library covers the shape; the generic kernel keeps the rest)
         self.fc_tail = self.h16 and _os.environ.get("GDRN_FC_TAIL", "1") != "0"   # (A/B, r6) fc2 finish + fc_r | fc_t + pose decode as one launch; seeded train step
         self.wgrad_side_lds = 84 * 1024
         self.stem_direct = self.h16   # the dedicated stem kernels, forward and (fused with bn1's backward apply) weight gradient
@@ -312,13 +309,13 @@ class Engine:
         L.wfmt = {"f": 0, "d": 0}
         if kind == "conv" and KK == 9 and not s2 and self.use_halo:  # halo-kernel operands (fragment-major)
             L.wfF, L.wdF = torch.zeros_like(L.wf), torch.zeros_like(L.wd)
-        elif kind == "conv" and KK == 9 and s2 and self.s2_halo:
+        elif kind == "conv" and KK == 9 and s2 and self.h16:
             # stride-2 3x3 layers (r6, csrc/conv3x3s2.hip, conv3x3s2_dgrad.hip): both operands also in the fragment-major layout (gdrn_pack_wfrag);
-            # the generic-layout copies stay (maps narrower than 16 pixels keep the generic kernel)
+            # the generic-layout copies stay (the generic kernel keeps the shapes those do not cover: odd batch sizes on 8-wide maps)
             L.wfF = torch.zeros_like(L.wf)
             L.wdF = torch.zeros_like(L.wd)   # ... and the data-gradient operand (taps not flipped) for gdrn_conv3x3s2_dgrad
             L.wfmt["f"] = L.wfmt["d"] = 1
-        elif kind == "convT" and KK == 9 and self.s2_halo:
+        elif kind == "convT" and KK == 9 and self.h16:
             # the head's ConvTranspose2d(3, stride 2, pad 1, output_padding 1): its FORWARD pass is the sum gdrn_conv3x3s2_dgrad evaluates
             # (dy = its input, rows = its output channels, taps not flipped = `wf`): the fragment-major copy of the forward operand
             L.wfF = torch.zeros_like(L.wf)

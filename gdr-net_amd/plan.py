@@ -3,6 +3,10 @@ configuration of one Engine (engine.py).  `Plan._build` walks the fixed graph on
 geometric head, head tail, Patch-PnP, pose decode, losses (core/gdrn_modeling/models/GDRN.py:110-306, resnet_backbone.py:69-80,
 cdpn_rot_head_region.py:182-193, conv_pnp_net.py:111-157) -- and appends one closure per kernel launch to `fwd` and, group by group in
 reverse, to `bwd`; `run_forward` / `run_backward` replay them on the current HIP stream (and the engine's side stream).
+The stage builders bind launches through the launch builders above them, one per kernel family: `_conv` (stride-1 halo kernel | generic kernel),
+`_s2` (gdrn_conv3x3s2) and `_s2d` (gdrn_conv3x3s2_dgrad), each returning (op, statistics rows) -- the stride-2 pair None where the library does not
+cover the shape --, `_wgrad`, and the BatchNorm glue `_bn_fwd` / `_bn_bwd`.  An op is a plain callable op(stream, ctx) that may carry `meta` (bench.py's
+roofline record), `parts` (a conv paired with its BatchNorm-coefficient launch, `_with_coef`), `side` / `defer` / `bucket_end` (stream placement) and `seed`.
 tools/plan_trace.py writes every launch of a plan with every argument as text, on the CPU: diff it across a change of this file."""
 import ctypes as C
 from types import SimpleNamespace as NS
@@ -28,6 +32,37 @@ def _launch(fn, what, args, meta=None):
     if meta is not None:
         run.meta = meta
     return run
+
+
+def _launch_struct(fn, what, params, meta=None):
+    """a launch whose arguments travel in a parameter struct: fn(byref(params), stream).  The plan keeps the struct alive (Plan.keep)."""
+    ref = C.byref(params)
+
+    def run(st, ctx):
+        s = fn(ref, st)
+        if s:
+            check(s, what)
+
+    if meta is not None:
+        run.meta = meta
+    return run
+
+
+def _bnb(key, raw, mask=None, affine=False):
+    """the BatchNorm(+ReLU) whose output gradient a data-gradient launch writes: the launch's epilogue masks the gradient and reduces that
+    BatchNorm's backward sums.  key: of the BatchNorm, raw: its input, mask: the stored activation the ReLU mask is read from, or None with
+    affine=True: the mask is recomputed from raw * scale + shift (BatchNorm -> ReLU without a residual)"""
+    return NS(key=key, raw=raw, mask=mask, affine=affine)
+
+
+def _xf_bn_relu(s, **kw):
+    """operand transform (xf of Plan._conv) of a conv that applies BatchNorm s + ReLU to its input on load"""
+    return dict(mode=1, a=s.scale, c=s.shift, relu=True, **kw)
+
+
+def _pend(x1, xf):
+    """an activation that is not materialised yet: v(x1) of the transform xf, evaluated (and written out) by the conv that consumes it"""
+    return NS(x1=x1, xf=xf)
 
 
 def _probed(op, sink):
@@ -99,11 +134,71 @@ class Plan:
             self.eval_prep.append(lambda st, ctx: self.e.eval_refresh())
             self._fold_hooked = True
 
+    def _macs(self, L, npix):
+        """true (unpadded) multiply-adds of layer L, whichever of its three products a launch computes.  npix: pixels per image of the smaller of
+        its two maps -- the output of a conv (also of the 7x7 stem and of fc1, a conv onto one pixel), the input of the ConvTranspose
+        (Hin*Win*Cin*Cout*k^2)"""
+        return self.B * npix * L.O * L.I * L.KK
+
+    @staticmethod
+    def _meta(kernel, macs, nbytes, layer):
+        """an op's record for the roofline measurement in bench.py: kernel instantiation, algorithmic FLOPs and bytes (SURVEY 8(d) convention:
+        activations in + out once, weights once, at the storage width)"""
+        return dict(kernel=kernel, flops=2.0 * macs, bytes=float(nbytes), layer=layer)
+
+    def _fill_bnb(self, p, bnb):
+        """the BatchNorm-backward epilogue fields of a ConvParams / S2Params / S2dParams from a _bnb record"""
+        sb = self.bn[bnb.key]
+        p.bnb_x, p.bnb_mask, p.bnb_cs = ptr(bnb.raw), ptr(bnb.mask), bnb.raw.shape[-1]
+        p.bnb_mean, p.bnb_invstd, p.bnb_rows = ptr(sb.mean), ptr(sb.invstd), ptr(self.stats)  # stats scratch is idle in backward
+        if bnb.affine:
+            assert hasattr(p, "bnb_scale"), type(p).__name__
+            p.bnb_scale, p.bnb_shift = ptr(sb.scale), ptr(sb.shift)
+
+    def _with_coef(self, conv, bnkey, nrows):
+        """conv: a data-gradient launch whose epilogue left nrows rows of BatchNorm bnkey's backward sums in self.stats.  Returns the pair (conv,
+        coefficient launch): rows -> that BatchNorm's backward coefficients (+ dgamma / dbeta), for its apply pass or for the conv that applies
+        them on load"""
+        assert 0 < nrows and nrows * 2 * self.bn[bnkey].C <= self.stats.numel(), (bnkey, nrows)
+        coef = self._bn_coef_op(bnkey, self.stats, nrows)
+
+        def run(st, ctx):
+            conv(st, ctx)
+            coef(st, ctx)
+
+        run.parts = (conv, coef)  # (the conv launch alone, what follows it): bench.py times the kernel, not the pair
+        run.meta = conv.meta
+        return run
+
+    def _halo_layer(self, L):
+        """does layer L run on the stride-1 3x3 halo kernel in this plan?"""
+        e = self.e
+        # (fp32 parity mode: only plans of the BASELINE sizes, see Engine.__init__)
+        return e.use_halo and self.B >= e.halo_min_b and L.kind == "conv" and L.wfF is not None and not L.s2
+
+    def _operand_layout(self, L, cp, which, npix):
+        """w_frag of a halo launch cp: the layout of layer L's operand copy `which` ("f" forward, "d" data gradient, "e" eval mode, BatchNorm folded
+        in), negotiated with the library by the first plan that uses the copy.  npix: output pixels per image."""
+        e = self.e
+        # the operand's layout is a property of the LAYER, not of whichever plan happens to be built first (ADVICE r3: a bs = 4 smoke
+        # plan used to pin the first halo kernel's layout for the bs = 64 training plan): the library is asked at the canonical batch
+        # size of the path (64 RoIs) unless this plan is bigger
+        m_plan = cp.M
+        cp.M = max(cp.M, 64 * npix)
+        cp.w_frag = e.v3_policy   # (the query reads the policy from w_frag; the answer goes back into it below)
+        want = int(e.lib.gdrn_conv3x3_wfrag(C.byref(cp)))
+        cp.M = m_plan
+        if not L.wfmt.get(which):
+            L.wfmt[which] = want if want in (1, 2) else 1
+            e._pack_dirty = True    # the operand copy is (re)built in that layout by the next repack
+        cp.w_frag = L.wfmt[which]  # an operand has ONE layout: later plans (other batch sizes) follow the first one
+
     def _conv(self, L, x, xs, y, Hi, Wi, Ho, Wo, stride, pad, mode=0, w=None, rows=None, cin=None, cout=None, x_cs=None,
               y_cs=None, bias=None, addend=None, add_cs=0, act=0, out_f32=0, stats=None, KH=None, KW=None, bnb=None, evalw=False, xf=None):
-        """bnb = (bn key, raw input of that BN, stored activation or None, affine mask?): data-gradient launch whose
-        output is the gradient w.r.t. that BatchNorm(+ReLU)'s output -- the halo kernel's epilogue masks it and
-        accumulates the BN-backward sums (see _fusable), so the BN backward is only its apply pass.
+        """a launch of layer L on the stride-1 halo kernel (_halo_layer) or on the generic kernel.  w given: the layer's data gradient (operand
+        copy wd).  Returns (op, rows of BatchNorm statistics its epilogue writes).
+        bnb (_bnb): data-gradient launch whose output is the gradient w.r.t. that BatchNorm(+ReLU)'s output -- the epilogue masks it and
+        accumulates the BN-backward sums (see _fusable), so the BN backward is only its apply pass; the coefficient launch is paired with it.
         xf = dict(mode, x2, a, b, c, c2, msc, msh, out, relu): the conv's input is v(x, x2) evaluated while the patch is staged
         (gdrn_hip.h, xf_mode), `out` (same shape as x) receives v -- halo launches only."""
         e = self.e
@@ -119,8 +214,10 @@ class Plan:
         cp.M = self.B * (Ho // 2) * (Wo // 2) if mode == 1 else self.B * Ho * Wo
         cp.w_rows = rows or L.rows_f
         cp.dtype = e.dt
-        if bnb is not None and bnb[2] is not None:
-            cp.bnb_mask = ptr(bnb[2])
+        halo = self._halo_layer(L)
+        if bnb is not None:
+            assert halo or e.gemm_bnb, L.key
+            self._fill_bnb(cp, bnb)
         if xf is not None:
             cp.xf_mode = xf["mode"]     # (the library's kernel choice depends on addend, stored mask and operand transform)
         # eight-wave form of the small-map tile (gdrn_hip.h, halo_waves): the library's choice in the forward pass and in inference (r5, isolated:
@@ -131,92 +228,36 @@ class Plan:
         cp.v3_min_wg = e.v3_min_wg
         self.keep.append(cp)
         ref = C.byref(cp)
-        halo_on = e.use_halo and self.B >= e.halo_min_b   # (fp32 parity mode: only plans of the BASELINE sizes, see Engine.__init__)
-        if halo_on and L.kind == "conv" and L.wfF is not None and not L.s2:
-            which = "e" if evalw else ("f" if w is None else "d")
-            # the operand's layout is a property of the LAYER, not of whichever plan happens to be built first (a bs = 4 smoke
-            # plan used to pin the first halo kernel's layout for the bs = 64 training plan): the library is asked at the canonical batch
-            # size of the path (64 RoIs) unless this plan is bigger
-            m_plan = cp.M
-            cp.M = max(cp.M, 64 * Ho * Wo)
-            cp.w_frag = e.v3_policy   # (the query reads the policy from w_frag; the answer goes back into it below)
-            want = int(e.lib.gdrn_conv3x3_wfrag(ref))
-            cp.M = m_plan
-            if not L.wfmt.get(which):
-                L.wfmt[which] = want if want in (1, 2) else 1
-                e._pack_dirty = True    # the operand copy is (re)built in that layout by the next repack
-            cp.w_frag = L.wfmt[which]  # an operand has ONE layout: later plans (other batch sizes) follow the first one
-        # 3x3 stride-1 layers (forward and data-gradient) run on the halo-tiled kernel
+        if halo:
+            self._operand_layout(L, cp, "e" if evalw else ("f" if w is None else "d"), Ho * Wo)
         th, tw, hbn = C.c_int(0), C.c_int(0), C.c_int(0)
         e.lib.gdrn_conv3x3_tile(ref, C.byref(th), C.byref(tw), C.byref(hbn))
-        use_halo = halo_on and th.value > 0 and L.kind == "conv" and L.wfF is not None and not L.s2
-        if halo_on and L.kind == "conv" and L.wfF is not None and not L.s2 and not use_halo:
+        if halo and th.value <= 0:
             raise RuntimeError(f"{L.key}: no halo tiling for {Hi}x{Wi} (the generic-layout operand copy is not maintained)")
         if evalw:      # eval-mode operand with the BatchNorm scale folded in (Engine.fold)
             assert w is None
-            cp.w = ptr(L.wfF_e if use_halo else L.wf_e)
-        elif use_halo:  # fragment-major operand copy (forward: of wf, data gradient: of wd)
+            cp.w = ptr(L.wfF_e if halo else L.wf_e)
+        elif halo:     # fragment-major operand copy (forward: of wf, data gradient: of wd)
             cp.w = ptr(L.wfF if w is None else L.wdF)
-        if bnb is not None:
-            assert use_halo or e.gemm_bnb, L.key
-            bkey, braw, bmask, baffine = bnb
-            sb = self.bn[bkey]
-            cp.bnb_x, cp.bnb_mask, cp.bnb_cs = ptr(braw), ptr(bmask), braw.shape[-1]
-            cp.bnb_mean, cp.bnb_invstd, cp.bnb_rows = ptr(sb.mean), ptr(sb.invstd), ptr(self.stats)  # stats scratch is idle in backward
-            if baffine:
-                cp.bnb_scale, cp.bnb_shift = ptr(sb.scale), ptr(sb.shift)
         if xf is not None:
-            assert use_halo and e.h16, L.key
+            assert halo and e.h16, L.key
             assert xf["out"] is None or (xf["out"].shape == x.shape and xf["out"].dtype == x.dtype), L.key
             assert xf.get("x2") is None or xf["x2"].shape == x.shape, L.key
             cp.xf_mode, cp.xf_relu = xf["mode"], 1 if xf.get("relu") else 0
             cp.xf_x2, cp.xf_a, cp.xf_b, cp.xf_c, cp.xf_c2 = ptr(xf.get("x2")), ptr(xf.get("a")), ptr(xf.get("b")), ptr(xf["c"]), ptr(xf.get("c2"))
             cp.xf_msc, cp.xf_msh, cp.xf_out = ptr(xf.get("msc")), ptr(xf.get("msh")), ptr(xf.get("out"))
-        fn = e.lib.gdrn_conv3x3_halo if use_halo else e.lib.gdrn_conv_gemm
-        cp._stats_rows = (e.lib.gdrn_conv3x3_stats_rows if use_halo else e.lib.gdrn_conv_stats_rows)(ref)
-
-        if bnb is not None:
-            nrows_b = int(cp._stats_rows)
-            assert nrows_b * 2 * cp.Cout <= self.stats.numel(), (L.key, nrows_b)
-            # the epilogue's per-tile rows -> that BatchNorm's backward coefficients (+ dgamma / dbeta), for its apply pass or
-            # for the conv that applies them on load
-            coef = self._bn_coef_op(bnb[0], self.stats, nrows_b)
-
-            def conv_only(st, ctx):
-                s = fn(ref, st)
-                if s:
-                    check(s, f"conv {L.key}")
-
-            def run(st, ctx):
-                conv_only(st, ctx)
-                coef(st, ctx)
-
-            run.parts = (conv_only, coef)  # (the conv launch alone, what follows it): bench.py times the kernel, not the pair
-        else:
-            def run(st, ctx):
-                s = fn(ref, st)
-                if s:
-                    check(s, f"conv {L.key}")
-
-        run.meta = self._conv_meta(L, cp, (th.value, tw.value, hbn.value) if use_halo else None, Hi, Wi, Ho, Wo, mode, w is not None)
-        return run, cp
+        nrows = int((e.lib.gdrn_conv3x3_stats_rows if halo else e.lib.gdrn_conv_stats_rows)(ref))
+        op = _launch_struct(e.lib.gdrn_conv3x3_halo if halo else e.lib.gdrn_conv_gemm, f"conv {L.key}", cp,
+                            self._conv_meta(L, cp, (th.value, tw.value, hbn.value) if halo else None, Hi, Wi, Ho, Wo, mode, w is not None))
+        return (op if bnb is None else self._with_coef(op, bnb.key, nrows)), nrows
 
     def _conv_meta(self, L, cp, halo_tile, Hi, Wi, Ho, Wo, mode, dgrad):
-        """metadata of a _conv launch for the roofline measurement in bench.py: kernel instantiation + algorithmic FLOPs and bytes.
-        halo_tile: (th, tw, hbn) of a halo launch, None for the generic kernel; dgrad: the launch is the layer's data gradient."""
+        """metadata of a _conv launch: halo_tile: (th, tw, hbn) of a halo launch, None for the generic kernel; dgrad: the launch is the layer's
+        data gradient."""
         e, ref = self.e, C.byref(cp)
         bm, bn = C.c_int(0), C.c_int(0)
         e.lib.gdrn_conv_tile(ref, C.byref(bm), C.byref(bn))
-        # true (unpadded) MACs: the layer's forward MAC count whichever direction this launch computes
-        if L.kind == "stem":
-            macs = self.B * 128 * 128 * 64 * 3 * 49
-        elif L.kind == "fc1":
-            macs = self.B * L.O * L.I * L.KK
-        else:
-            sp = (Ho * Wo) if (mode == 0 and (not dgrad or L.kind == "convT")) else (Hi * Wi)
-            if L.kind == "convT":
-                sp = 8 * 8  # Hin*Win*Cin*Cout*k^2 (SURVEY.md section 8(d))
-            macs = self.B * sp * L.O * L.I * L.KK
+        small = (Ho * Wo) if (mode == 0 and (not dgrad or L.kind == "convT")) else (Hi * Wi)   # (mode 1 and the ConvTranspose's forward: the input map)
         dn = "bf16" if e.h16 else "f32"   # (the 16-bit instantiation: its name in a trace is the same in both library builds)
         th, tw, hbn = halo_tile or (0, 0, 0)
         if halo_tile and cp.w_frag == 2:
@@ -225,176 +266,92 @@ class Plan:
             kname = f"conv3x3_halo_kernel<{dn},{th},{tw},{hbn},{cp.xf_mode},{int(e.lib.gdrn_conv3x3_halo_waves(ref)) // 4}>"
         else:
             kname = f"conv_gemm_kernel<{dn},{bm.value},{bn.value}>"
-        # algorithmic bytes (SURVEY 8(d) convention: activations in + out once, weights once, at the storage width)
-        esz = 2 if e.h16 else 4
-        nbytes = (self.B * Hi * Wi * cp.Cin + self.B * Ho * Wo * cp.Cout) * esz + cp.Cout * cp.Cin * cp.KH * cp.KW * esz
-        return dict(kernel=kname, flops=2.0 * macs, bytes=float(nbytes), layer=L.key + (":dgrad" if dgrad else ""))
+        return self._meta(kname, self._macs(L, small), (self.B * Hi * Wi * cp.Cin + self.B * Ho * Wo * cp.Cout + cp.Cout * cp.Cin * cp.KH * cp.KW) * e.esz,
+                          L.key + (":dgrad" if dgrad else ""))
 
-    def _s2(self, L, x, x_cs, y, Hi, Ho, Ld=None, yd=None, stats=None, stats_d=None, bias=None, bias_d=None, act=0, evalw=False):
-        """forward launch of a 3x3 stride-2 conv on the parity-plane halo kernel (gdrn_conv3x3s2), with the block's 1x1 shortcut conv Ld in the
-        same launch when given.  Returns (op, NS(_stats_rows) of the main conv, the same for the shortcut) or None when the library does not
-        cover the shape (maps narrower than 16 pixels: the generic kernel keeps them)."""
+    def _s2(self, L, which, x, y, Hi, Ho, Ld=None, yd=None, stats=None, stats_d=None, bias=None, bias_d=None, act=0, bnb=None):
+        """a launch of the parity-plane halo kernel gdrn_conv3x3s2, a 3x3 stride-2 pad-1 conv x [B, Hi, Hi, .] -> y [B, Ho = Hi / 2, Ho, .], on operand
+        copy `which` of layer L:
+          "f" / "e" (eval mode, BatchNorm folded in)  the forward pass of a stage-entry or Patch-PnP conv, with the block's 1x1 shortcut conv Ld -> yd
+                                                      in the same launch when given; epilogue: statistics rows (stats, stats_d) or bias + activation
+          "d"                                         the data gradient of the head's ConvTranspose2d (x = its output gradient), with the
+                                                      BatchNorm-backward epilogue bnb (_bnb) and the coefficient launch behind it (as in _conv)
+        Returns (op, statistics rows -- of the main conv and of the shortcut alike) or None when the library does not cover the shape (the generic
+        kernel keeps it)."""
         e = self.e
-        if not (e.s2_halo and L.wfF is not None and L.s2) or (Ho < 16 and not e.s2_tw8):
+        w = getattr(L, {"f": "wfF", "e": "wfF_e", "d": "wdF"}[which], None)
+        if not e.h16 or w is None:
             return None
+        dgrad = which == "d"
+        cin, cout, w_rows = (L.cin_d, L.I, L.rows_d) if dgrad else (L.cin_f, L.O, L.rows_f)
         sp = S2Params()
-        sp.x, sp.y = ptr(x), ptr(y)
-        sp.w = ptr(L.wfF_e if evalw else L.wfF)
-        sp.bias, sp.stats = ptr(bias), ptr(stats)
+        sp.x, sp.w, sp.y = ptr(x), ptr(w), ptr(y)
+        sp.bias, sp.stats, sp.act = ptr(bias), ptr(stats), act
         if Ld is not None:
-            sp.wd, sp.yd, sp.bias_d, sp.stats_d = ptr(Ld.wf_e if evalw else Ld.wf), ptr(yd), ptr(bias_d), ptr(stats_d)
+            sp.wd, sp.yd, sp.bias_d, sp.stats_d = ptr(Ld.wf_e if which == "e" else Ld.wf), ptr(yd), ptr(bias_d), ptr(stats_d)
             sp.yd_cs, sp.wd_rows = yd.shape[-1], Ld.rows_f
             assert Ld.cin_f == L.cin_f, (L.key, Ld.key)
+        if bnb is not None:
+            self._fill_bnb(sp, bnb)
         sp.Hi = sp.Wi = Hi
         sp.Ho = sp.Wo = Ho
-        sp.Cin, sp.x_cs, sp.Cout, sp.y_cs = L.cin_f, x_cs, L.O, y.shape[-1]
-        sp.N, sp.w_rows, sp.act, sp.dtype = self.B, L.rows_f, act, e.dt
-        ref = C.byref(sp)
-        if not int(e.lib.gdrn_conv3x3s2_ok(ref)):
+        sp.Cin, sp.x_cs, sp.Cout, sp.y_cs = cin, x.shape[-1], cout, y.shape[-1]
+        sp.N, sp.w_rows, sp.dtype = self.B, w_rows, e.dt
+        if not int(e.lib.gdrn_conv3x3s2_ok(C.byref(sp))):
             return None
         self.keep.append(sp)
-        rows = int(e.lib.gdrn_conv3x3s2_stats_rows(ref))
-        for st_, c_ in ((stats, L.O), (stats_d, L.O)):
-            assert st_ is None or rows * 2 * c_ <= st_.numel(), (L.key, rows)
+        nrows = int(e.lib.gdrn_conv3x3s2_stats_rows(C.byref(sp)))
+        role = " (data gradient)" if dgrad else ""
+        maps = 1 + (Ld is not None) + (bnb is not None)   # Cout-wide maps moved: y, the shortcut's yd, the BatchNorm input the epilogue reads
+        meta = self._meta(f"conv3x3s2_kernel<{'true' if Ld is not None else 'false'}>" + role,
+                          self._macs(L, Ho * Ho) + (self._macs(Ld, Ho * Ho) if Ld is not None else 0),
+                          (self.B * Hi * Hi * cin + maps * self.B * Ho * Ho * cout + cout * cin * 9) * 2,
+                          L.key + (":dgrad" if dgrad else "") + ("+downsample" if Ld is not None else ""))
+        op = _launch_struct(e.lib.gdrn_conv3x3s2, f"conv3x3s2{role} {L.key}", sp, meta)
+        return (op if bnb is None else self._with_coef(op, bnb.key, nrows)), nrows
 
-        def run(st, ctx):
-            s_ = e.lib.gdrn_conv3x3s2(ref, st)
-            if s_:
-                check(s_, f"conv3x3s2 {L.key}")
-
-        macs = self.B * Ho * Ho * L.O * L.I * 9 + (self.B * Ho * Ho * Ld.O * Ld.I if Ld is not None else 0)
-        esz = 2
-        run.meta = dict(kernel=f"conv3x3s2_kernel<{'true' if Ld is not None else 'false'}>", flops=2.0 * macs,
-                        bytes=float((self.B * Hi * Hi * L.cin_f + (2 if Ld is not None else 1) * self.B * Ho * Ho * L.O) * esz + L.O * L.cin_f * 9 * esz),
-                        layer=L.key + ("+downsample" if Ld is not None else ""))
-        return run, NS(_stats_rows=rows), NS(_stats_rows=rows)
-
-    def _s2d(self, L, dy, dx, Ho, Hi, cin, Ld=None, dyd=None, bnb=None):
-        """data-gradient launch of a 3x3 stride-2 conv on gdrn_conv3x3s2_dgrad: dx [B, Hi, Hi, cin] from dy [B, Ho, Ho, L.O]; Ld / dyd: the block's
-        1x1 shortcut conv and ITS output gradient, added in the same launch; bnb = (bn key, raw input of that BatchNorm, stored activation): dx is
-        the gradient w.r.t. that BatchNorm(+ReLU)'s output -- masked, its backward sums reduced in the epilogue, and the coefficient launch
-        appended (as _conv does for its bnb).  None when the library does not cover the shape."""
+    def _s2d(self, L, which, dy, dx, Ho, Hi, Ld=None, dyd=None, bnb=None, stats=None, bias=None, act=0):
+        """a launch of the parity-class kernel gdrn_conv3x3s2_dgrad, dy [B, Ho, Ho, .] -> dx [B, Hi = 2 Ho, Hi, .], on operand copy `which` of layer L:
+          "d"        the data gradient of a 3x3 stride-2 conv; Ld / dyd: the block's 1x1 shortcut conv and ITS output gradient, added in the same
+                     launch; bnb (_bnb): dx is the gradient w.r.t. that BatchNorm(+ReLU)'s output -- masked, its backward sums reduced in the
+                     epilogue, and the coefficient launch paired with the conv (as in _conv)
+          "f" / "e"  the forward pass of the head's ConvTranspose2d(3, stride 2, pad 1, output_padding 1) -- the same sum -- with a forward epilogue:
+                     statistics rows (stats, train mode) or the folded BatchNorm's shift + ReLU (bias, act; eval mode)
+        Returns (op, rows the epilogue writes) or None when the library does not cover the shape."""
         e = self.e
-        if not (e.s2_halo and getattr(L, "wdF", None) is not None and L.s2) or (Ho < 16 and not e.s2_tw8):
+        w = getattr(L, {"f": "wfF", "e": "wfF_e", "d": "wdF"}[which], None)
+        if not e.h16 or w is None:
             return None
+        fwd = which != "d"
+        cin, cout, w_rows = (L.O, L.cin_f, L.rows_f) if fwd else (L.cin_f, L.cin_d, L.rows_d)   # (channels of dx, of dy)
         sp = S2dParams()
-        sp.dy, sp.w, sp.dx = ptr(dy), ptr(L.wdF), ptr(dx)
+        sp.dy, sp.w, sp.dx = ptr(dy), ptr(w), ptr(dx)
+        sp.bias, sp.stats, sp.act = ptr(bias), ptr(stats), act
         if Ld is not None:
             sp.dyd, sp.wdd, sp.dyd_cs, sp.wdd_rows = ptr(dyd), ptr(Ld.wd), dyd.shape[-1], Ld.rows_d
             assert Ld.cin_d == L.cin_d, (L.key, Ld.key)
         if bnb is not None:
-            bkey, braw, bmask = bnb
-            sb = self.bn[bkey]
-            sp.bnb_x, sp.bnb_mask, sp.bnb_mean, sp.bnb_invstd, sp.bnb_rows, sp.bnb_cs = ptr(braw), ptr(bmask), ptr(sb.mean), ptr(sb.invstd), ptr(self.stats), braw.shape[-1]
+            self._fill_bnb(sp, bnb)
         sp.Hi = sp.Wi = Hi
         sp.Ho = sp.Wo = Ho
-        sp.Cin, sp.dx_cs, sp.Cout, sp.dy_cs = cin, dx.shape[-1], L.cin_d, dy.shape[-1]
-        sp.N, sp.w_rows, sp.dtype = self.B, L.rows_d, e.dt
-        ref = C.byref(sp)
-        if not int(e.lib.gdrn_conv3x3s2_dgrad_ok(ref)):
+        sp.Cin, sp.dx_cs, sp.Cout, sp.dy_cs = cin, dx.shape[-1], cout, dy.shape[-1]
+        sp.N, sp.w_rows, sp.dtype = self.B, w_rows, e.dt
+        if not int(e.lib.gdrn_conv3x3s2_dgrad_ok(C.byref(sp))):
             return None
         self.keep.append(sp)
-
-        def conv_only(st, ctx):
-            s_ = e.lib.gdrn_conv3x3s2_dgrad(ref, st)
-            if s_:
-                check(s_, f"conv3x3s2_dgrad {L.key}")
-
-        run = conv_only
-        if bnb is not None:
-            nrows = int(e.lib.gdrn_conv3x3s2_dgrad_rows(ref))
-            assert nrows * 2 * cin <= self.stats.numel(), (L.key, nrows)
-            coef = self._bn_coef_op(bnb[0], self.stats, nrows)
-
-            def run(st, ctx):
-                conv_only(st, ctx)
-                coef(st, ctx)
-
-            run.parts = (conv_only, coef)
-        macs = self.B * Ho * Ho * L.O * L.I * 9 + (self.B * Ho * Ho * Ld.O * Ld.I if Ld is not None else 0)
-        run.meta = dict(kernel=f"conv3x3s2_dgrad_kernel<{'true' if Ld is not None else 'false'},{'true' if bnb is not None else 'false'}>", flops=2.0 * macs,
-                        bytes=float((self.B * Hi * Hi * cin + (2 if Ld is not None else 1) * self.B * Ho * Ho * L.cin_d) * 2 + L.cin_d * cin * 9 * 2),
-                        layer=L.key + ":dgrad" + ("+downsample:dgrad" if Ld is not None else ""))
-        return run
-
-    def _convT_dgrad(self, LT, dy, dx, Hi, Ho, bnb):
-        """data gradient of the head's ConvTranspose2d = a 3x3 stride-2 pad-1 conv of the output gradient dy [B, Hi, Hi, LT.O] -> dx [B, Ho = Hi / 2, Ho,
-        LT.cin_f] on gdrn_conv3x3s2 with the BatchNorm-backward epilogue (bnb = (bn key, raw input of that BatchNorm, stored activation)) and the
-        coefficient launch behind it.  None when the library does not cover the shape."""
-        e = self.e
-        if not (e.s2_halo and e.s2_tw8 and LT.kind == "convT" and getattr(LT, "wdF", None) is not None):
-            return None
-        bkey, braw, bmask = bnb
-        sb = self.bn[bkey]
-        sp = S2Params()
-        sp.x, sp.w, sp.y = ptr(dy), ptr(LT.wdF), ptr(dx)
-        sp.Hi = sp.Wi = Hi
-        sp.Ho = sp.Wo = Ho
-        sp.Cin, sp.x_cs, sp.Cout, sp.y_cs = LT.cin_d, dy.shape[-1], LT.I, dx.shape[-1]
-        sp.N, sp.w_rows, sp.dtype = self.B, LT.rows_d, e.dt
-        sp.bnb_x, sp.bnb_mask, sp.bnb_mean, sp.bnb_invstd, sp.bnb_rows, sp.bnb_cs = ptr(braw), ptr(bmask), ptr(sb.mean), ptr(sb.invstd), ptr(self.stats), braw.shape[-1]
-        ref = C.byref(sp)
-        if not int(e.lib.gdrn_conv3x3s2_ok(ref)):
-            return None
-        self.keep.append(sp)
-        nrows = int(e.lib.gdrn_conv3x3s2_stats_rows(ref))
-        assert nrows * 2 * LT.I <= self.stats.numel(), (LT.key, nrows)
-        coef = self._bn_coef_op(bkey, self.stats, nrows)
-
-        def conv_only(st, ctx):
-            s_ = e.lib.gdrn_conv3x3s2(ref, st)
-            if s_:
-                check(s_, f"conv3x3s2 (data gradient) {LT.key}")
-
-        def run(st, ctx):
-            conv_only(st, ctx)
-            coef(st, ctx)
-
-        run.parts = (conv_only, coef)
-        run.meta = dict(kernel="conv3x3s2_kernel<false> (data gradient)", flops=2.0 * self.B * Ho * Ho * LT.O * LT.I * 9,
-                        bytes=float((self.B * Hi * Hi * LT.O + 2 * self.B * Ho * Ho * LT.I) * 2 + LT.O * LT.I * 9 * 2), layer=LT.key + ":dgrad")
-        return run
-
-    def _convT_fwd(self, LT, bnkey, x, y, Hi, Ho, stats=None, evalmode=False):
-        """forward launch of the head's ConvTranspose2d(3, stride 2, pad 1, output_padding 1) on gdrn_conv3x3s2_dgrad (the same sum as a stride-2
-        conv's data gradient: x [B, Hi, Hi, LT.cin_f] -> y [B, Ho = 2 Hi, Ho, LT.O]) with a forward epilogue: statistics rows (train mode) or the
-        folded BatchNorm's shift + ReLU (evalmode).  Returns (op, NS(_stats_rows)) or None when the library does not cover the shape."""
-        e = self.e
-        if not (e.s2_halo and LT.kind == "convT" and getattr(LT, "wfF", None) is not None) or (Hi < 16 and not e.s2_tw8):
-            return None
-        sp = S2dParams()
-        sp.dy, sp.dx = ptr(x), ptr(y)
-        sp.Hi = sp.Wi = Ho
-        sp.Ho = sp.Wo = Hi
-        sp.Cin, sp.dx_cs, sp.Cout, sp.dy_cs = LT.O, y.shape[-1], LT.cin_f, x.shape[-1]
-        sp.N, sp.w_rows, sp.dtype = self.B, LT.rows_f, e.dt
-        sp.w = ptr(LT.wfF)
-        ref = C.byref(sp)
-        if not int(e.lib.gdrn_conv3x3s2_dgrad_ok(ref)):
-            return None
-        if evalmode:
-            f = e.fold(bnkey, LT)
-            self._hook_fold()
-            sp.w, sp.bias, sp.act = ptr(LT.wfF_e), ptr(f.shift), 1
-        else:
-            sp.stats = ptr(stats)
-        self.keep.append(sp)
-        rows = int(e.lib.gdrn_conv3x3s2_dgrad_rows(ref))
-        assert stats is None or rows * 2 * LT.O <= stats.numel(), (LT.key, rows)
-
-        def run(st, ctx):
-            s_ = e.lib.gdrn_conv3x3s2_dgrad(ref, st)
-            if s_:
-                check(s_, f"conv3x3s2_dgrad (forward) {LT.key}")
-
-        run.meta = dict(kernel="conv3x3s2_dgrad_kernel<false,false> (forward)", flops=2.0 * self.B * Hi * Hi * LT.O * LT.I * 9,
-                        bytes=float((self.B * Ho * Ho * LT.O + self.B * Hi * Hi * LT.cin_f) * 2 + LT.O * LT.cin_f * 9 * 2), layer=LT.key)
-        return run, NS(_stats_rows=rows)
-
-    def _stats_rows(self, cp):
-        return cp._stats_rows
+        nrows = int(e.lib.gdrn_conv3x3s2_dgrad_rows(C.byref(sp)))
+        role = " (forward)" if fwd else ""
+        tf = lambda b: "true" if b else "false"
+        meta = self._meta(f"conv3x3s2_dgrad_kernel<{tf(Ld is not None)},{tf(bnb is not None)}>" + role,
+                          self._macs(L, Ho * Ho) + (self._macs(Ld, Ho * Ho) if Ld is not None else 0),
+                          (self.B * Hi * Hi * cin + (2 if Ld is not None else 1) * self.B * Ho * Ho * cout + cout * cin * 9) * 2,
+                          L.key + ("" if fwd else ":dgrad") + ("+downsample:dgrad" if Ld is not None else ""))
+        op = _launch_struct(e.lib.gdrn_conv3x3s2_dgrad, f"conv3x3s2_dgrad{role} {L.key}", sp, meta)
+        return (op if bnb is None else self._with_coef(op, bnb.key, nrows)), nrows
 
     def _wgrad(self, L, x, dy, Hi, Wi, Ho, Wo, stride, pad, cin, cout, x_cs, dy_cs, KH=None, KW=None, defer=False):
+        """the weight gradient of layer L: deferred to its bucket's grouped launch (returns None) where the 3x3 halo kernel covers it, else a
+        side-stream launch of the generic kernel"""
         e = self.e
         wp = WgradParams()
         wp.x, wp.dy, wp.dw = ptr(x), ptr(dy), ptr(L.dwp)
@@ -403,37 +360,21 @@ class Plan:
         wp.KH, wp.KW, wp.stride, wp.pad = KH or L.KH, KW or L.KW, stride, pad
         wp.M, wp.dtype, wp.splits, wp.variant = self.B * Ho * Wo, e.dt, 0, 0
         self.keep.append(wp)
-        ref = C.byref(wp)
         # halo-tiled kernel: every 3x3 pad-1 conv, stride 1 or 2 (incl. Patch-PnP's and, roles swapped, the head's ConvTranspose)
-        use_halo = e.use_halo and L.kind in ("conv", "convT") and L.KK == 9 and bool(e.lib.gdrn_conv3x3_wgrad_ok(ref))
-        fn = e.lib.gdrn_conv3x3_wgrad if use_halo else e.lib.gdrn_conv_wgrad
-        if use_halo:
+        if e.use_halo and L.kind in ("conv", "convT") and L.KK == 9 and bool(e.lib.gdrn_conv3x3_wgrad_ok(C.byref(wp))):
             # deferred: one grouped launch per gradient bucket (see _finish_unpack) -- weight gradients are off the
             # critical path, and a grid over many layers fills the chip with far fewer pixel-range splits per layer
             # (flops, algorithmic bytes: X and dY read once at the storage width, the fp32 gradient written once)
-            self._wgrad_deferred.append((len(self.bwd_groups), L, wp, (2.0 * self.B * Ho * Wo * L.O * L.I * L.KK,
+            self._wgrad_deferred.append((len(self.bwd_groups), L, wp, (2.0 * self._macs(L, Ho * Wo),
                                                                       2.0 * self.B * (Hi * Wi * cin + Ho * Wo * cout) + 4.0 * cout * cin * 9)))
             return None
 
         self._zero_regions.append(self._pad16(L.dwp, e.dwp_flat))  # accumulated with fp32 atomics
-
-        def run(st, ctx):
-            s = fn(ref, st)
-            if s:
-                check(s, f"conv_wgrad {L.key}")
-
-        if L.kind == "stem":
-            macs = self.B * 128 * 128 * 64 * 3 * 49
-        elif L.kind == "convT":
-            macs = self.B * 64 * L.O * L.I * L.KK
-        else:
-            macs = self.B * Ho * Wo * L.O * L.I * L.KK
         bco, bci = (64 if cout <= 64 else 128), (128 if cin % 128 == 0 else 64)
-        kname = "conv3x3_wgrad_kernel" if use_halo else f"conv_wgrad_kernel<{'bf16' if e.h16 else 'f32'},{bco},{bci}>"
-        esz = 2 if e.h16 else 4
-        run.meta = dict(kernel=kname, flops=2.0 * macs, bytes=float(self.B * (Hi * Wi * cin + Ho * Wo * cout) * esz + 4 * cout * cin * wp.KH * wp.KW),
-                        layer=L.key + ":wgrad")
-        return self._side(run, defer)  # feeds only the optimizer: off the data-gradient chain (side stream, see run_backward)
+        meta = self._meta(f"conv_wgrad_kernel<{'bf16' if e.h16 else 'f32'},{bco},{bci}>", self._macs(L, Ho * Wo),
+                          self.B * (Hi * Wi * cin + Ho * Wo * cout) * e.esz + 4 * cout * cin * wp.KH * wp.KW, L.key + ":wgrad")
+        # feeds only the optimizer: off the data-gradient chain (side stream, see run_backward)
+        return self._side(_launch_struct(e.lib.gdrn_conv_wgrad, f"conv_wgrad {L.key}", wp, meta), defer)
 
     @staticmethod
     def _side(op, defer=False):
@@ -509,8 +450,9 @@ class Plan:
         self._unpack_pending.append((len(self.bwd_groups), L))
         return None  # marker, dropped when the groups are flattened
 
-    def _bn_fwd(self, bnkey, raw, cp, C_, npix, y, residual=None, relu=1, stats=None):
-        """finalize (train) or eval params, then apply.  Returns list of fwd ops.  stats: the producer's partial-row scratch (default self.stats)."""
+    def _bn_fwd(self, bnkey, raw, rows, C_, npix, y, residual=None, relu=1, stats=None):
+        """finalize (train) or eval params, then apply.  Returns list of fwd ops.  rows: partial rows of statistics the producing launch wrote (train
+        mode) to stats, its scratch (default self.stats)."""
         e, lib = self.e, self.e.lib
         stats = self.stats if stats is None else stats
         s = NS(mean=e._empty(C_, dtype=torch.float32), invstd=e._empty(C_, dtype=torch.float32),
@@ -520,7 +462,6 @@ class Plan:
         rm, rv, nbt = e.Bf[bnkey + ".running_mean"], e.Bf[bnkey + ".running_var"], e.Bf[bnkey + ".num_batches_tracked"]
         ops = []
         if self.bn_train:
-            rows = self._stats_rows(cp)
             assert rows * 2 * C_ <= stats.numel(), (bnkey, rows, C_)  # the producer's partial rows fit the scratch
             ops.append(_launch(lib.gdrn_bn_finalize, "bn_finalize", (stats, rows, C_, float(npix), g, b, rm, rv, nbt, 0.1, 1e-5, s.mean, s.invstd,
                                                                      s.scale, s.shift, e.bn_ws)))
@@ -534,7 +475,7 @@ class Plan:
 
     def _xf_ok(self, L):
         """can layer L's halo launches (forward and data gradient) take a fused operand transform?"""
-        return self.e.fuse_xf and self.bn_train and L.kind == "conv" and L.wfF is not None and L.KK == 9 and not L.s2
+        return self.e.fuse_xf and self.bn_train and self._halo_layer(L)   # (fuse_xf: 16-bit modes only, where every plan size runs the halo kernel)
 
     def _bn_coef_op(self, bnkey, rows, nrows):
         """rows [nrows][2][C] of BatchNorm-backward sums -> (ka, kb, kc) of dx = ka*g + kb*x + kc, dgamma, dbeta (one launch)."""
@@ -551,47 +492,47 @@ class Plan:
         """eval mode: conv -> BatchNorm (-> +residual) (-> ReLU) as ONE launch, y = act(conv_{w*scale}(x) + shift + residual)."""
         f = self.e.fold(bnkey, L)
         self._hook_fold()
-        op, _ = self._conv(L, x, xs, y, Hi, Wi, Ho, Wo, stride, pad, bias=f.shift, addend=residual, add_cs=add_cs, act=1 if relu else 0,
-                           evalw=True, **kw)
-        return op
+        return self._conv(L, x, xs, y, Hi, Wi, Ho, Wo, stride, pad, bias=f.shift, addend=residual, add_cs=add_cs, act=1 if relu else 0,
+                          evalw=True, **kw)[0]
 
     def _fusable(self, L):
-        """can the data gradient of layer L run on the halo kernel (and so carry a fused BN-backward reduction)?"""
+        """can the data gradient of layer L run on the halo kernel (and so carry a fused BN-backward reduction)?  Asked about stride-1 layers only."""
         e = self.e
+        # (not _halo_layer: True for the stride-2 3x3 layers as well, which hold a fragment-major copy for gdrn_conv3x3s2)
         return e.use_halo and e.h16 and L.kind == "conv" and L.wfF is not None
 
-    def _bn_bwd(self, bnkey, dy, ymask, raw, dx, g_out=None, affine_mask=False, prereduced=False, xf=False, apply=True, sums_done=False):
-        """BatchNorm(+ReLU) backward: [reduce -> coef ->] apply.  prereduced: dy arrives masked and the producing data-gradient
-        launch has already turned its epilogue rows into the coefficients (see _conv, bnb).
+    def _bn_bwd(self, bnkey, dy, ymask, raw, dx, g_out=None, affine_mask=False, sums="here", xf=False):
+        """BatchNorm(+ReLU) backward: [reduce -> coef ->] apply.  Returns (ops, xf): xf=True leaves the apply pass to the consumer halo conv --
+        the returned xf is that conv's operand transform (see _conv), which also writes dx; else None.
+        sums: who reduces the backward sums --
+          "here"      a reduce launch of this call, and the coefficient launch behind it
+          "dgrad"     the data-gradient launch that produced dy: dy arrives masked, and its epilogue rows have been turned into the coefficients
+                      already (see _conv, bnb)
+          "upsample"  the upsampling adjoint that produced dy (gdrn_upsample2x_bwd_bnsums): the rows are written, only the coefficient launch
+                      is left; dy itself is NOT masked
         affine_mask: BN -> ReLU without residual: the ReLU mask is recomputed from raw*scale+shift (what bn_apply
-        evaluated) instead of reading the stored activation `ymask` -- one tensor pass less in both kernels.
-        xf: the apply pass is left to the consumer halo conv (returns (ops, xf dict for _conv); dx is written by that conv).
-        apply=False: only reduce + coef (the stem's weight-gradient kernel applies the coefficients itself)."""
+        evaluated) instead of reading the stored activation `ymask` -- one tensor pass less in both kernels."""
         e, lib = self.e, self.e.lib
         s = self.bn[bnkey]
         msc, msh = (s.scale, s.shift) if affine_mask else (None, None)
         ym = None if affine_mask else ymask
         ops = []
-        if prereduced:
-            self._bn_coef_op(bnkey, self.stats, 1)  # (allocates the coefficient vectors; the launch itself sits in _conv)
+        if sums == "dgrad":
+            self._bn_coef_op(bnkey, self.stats, 1)  # (allocates the coefficient vectors; the launch itself sits in _with_coef)
             msc = msh = ym = None                    # dy is already masked
-        elif sums_done:
-            # the launch that produced dy (gdrn_upsample2x_bwd_bnsums) has written the reduction's rows already; dy itself is NOT masked
-            nrows = int(lib.gdrn_bn_bwd_reduce_rows(s.npix, s.C, e.dt))
-            assert nrows > 0 and nrows * 2 * s.C <= self.stats.numel(), (bnkey, nrows)
-            ops.append(self._bn_coef_op(bnkey, self.stats, nrows))
         else:
+            assert sums in ("here", "upsample"), sums
             nrows = int(lib.gdrn_bn_bwd_reduce_rows(s.npix, s.C, e.dt))
             assert nrows > 0 and nrows * 2 * s.C <= self.stats.numel(), (bnkey, nrows)
             coef = self._bn_coef_op(bnkey, self.stats, nrows)
-            ops += [_launch(lib.gdrn_bn_bwd_reduce, "bn_bwd_reduce", (dy, ym, raw, s.mean, s.invstd, msc, msh, s.npix, s.C, self.stats, e.dt)), coef]
+            if sums == "here":
+                ops.append(_launch(lib.gdrn_bn_bwd_reduce, "bn_bwd_reduce", (dy, ym, raw, s.mean, s.invstd, msc, msh, s.npix, s.C, self.stats, e.dt)))
+            ops.append(coef)
         if xf:
             assert g_out is None and ym is None
-            mode = 4 if msc is not None else 3
-            return ops, dict(mode=mode, x2=raw, a=s.ka, b=s.kb, c=s.kc, msc=msc, msh=msh, out=dx, relu=False)
-        if apply:
-            ops.append(_launch(lib.gdrn_bn_bwd_apply, "bn_bwd_apply", (dy, ym, raw, s.ka, s.kb, s.kc, msc, msh, s.npix, s.C, dx, g_out, e.dt)))
-        return ops
+            return ops, dict(mode=4 if msc is not None else 3, x2=raw, a=s.ka, b=s.kb, c=s.kc, msc=msc, msh=msh, out=dx, relu=False)
+        ops.append(_launch(lib.gdrn_bn_bwd_apply, "bn_bwd_apply", (dy, ym, raw, s.ka, s.kb, s.kc, msc, msh, s.npix, s.C, dx, g_out, e.dt)))
+        return ops, None
 
     def _unpack_task(self, L, packed_ptr, grad, rows_valid, rows_off=0):
         from .cabi import PackTask
@@ -772,17 +713,16 @@ class Plan:
         idx0 = None if fused_stem else E(B, 64, 64, 64, dtype=torch.uint8)
         flops = 2.0 * B * 128 * 128 * 64 * 147
         self.fwd.append(lambda st, ctx: check(lib.gdrn_pack_image(ctx["img"], ptr(self.img_p), B, 256, 256, 262, 272, e.dt, st), "pack_image"))
-        if fused_stem:
-            cp = None
-        elif e.stem_direct:
-            cp = NS(_stats_rows=int(lib.gdrn_stem_stats_rows(B)))
-            self.fwd.append(_launch(lib.gdrn_stem_conv, "stem_conv", (self.img_p, e.stem_w32, raw0, self.stats if S else None, B, e.dt),
+        rows = None   # (eval mode: no statistics)
+        if e.stem_direct and S:
+            rows = int(lib.gdrn_stem_stats_rows(B))
+            self.fwd.append(_launch(lib.gdrn_stem_conv, "stem_conv", (self.img_p, e.stem_w32, raw0, self.stats, B, e.dt),
                                     dict(kernel="stem_conv_kernel", flops=flops, layer="backbone.conv1")))
-        else:
-            op, cp = self._conv(Ls, self.img_p, 4, raw0, 262, 272, 128, 128, 2, 0, cin=64, cout=64, x_cs=4, KH=7, KW=1,
-                                stats=self.stats if S else None)
+        elif not fused_stem:
+            op, rows = self._conv(Ls, self.img_p, 4, raw0, 262, 272, 128, 128, 2, 0, cin=64, cout=64, x_cs=4, KH=7, KW=1,
+                                  stats=self.stats if S else None)
             self.fwd.append(op)
-        self.fwd += self._bn_fwd("backbone.bn1", raw0, cp, 64, B * 128 * 128, None)
+        self.fwd += self._bn_fwd("backbone.bn1", raw0, rows, 64, B * 128 * 128, None)
         s0 = self.bn["backbone.bn1"]
         if fused_stem:
             self.fwd.append(_launch(lib.gdrn_stem_conv_pool, "stem_conv_pool", (self.img_p, e.stem_w32, s0.scale, s0.shift, p0, B, e.dt),
@@ -814,7 +754,7 @@ class Plan:
                                dict(kernel="stem_wgrad_kernel", flops=flops, layer="backbone.conv1:wgrad")))
         else:
             grp = [_launch(lib.gdrn_maxpool_bwd, "maxpool_bwd", (d_p0, idx0, raw0, s0.scale, s0.shift, g_stem, B, 128, 128, 64, None, None, None, e.dt))]
-            grp += self._bn_bwd("backbone.bn1", g_stem, None, raw0, g_stem)   # (in place)
+            grp += self._bn_bwd("backbone.bn1", g_stem, None, raw0, g_stem)[0]   # (in place)
             grp.append(self._wgrad(Ls, self.img_p, g_stem, 262, 272, 128, 128, 2, 0, 64, 64, 4, 64, KH=7, KW=1))
             grp.append(self._unpack(Ls))
         self.bwd_groups.append(grp)
@@ -847,7 +787,7 @@ class Plan:
         e, lib, B = self.e, self.e.lib, self.B
         x, Hc, inpl = c.x, c.Hc, c.inpl
         pfx, pl, Ho, stride, L1, L2, Ld, a1, out = k.pfx, k.pl, k.Ho, k.stride, k.L1, k.L2, k.Ld, k.a1, k.out
-        if e.block64 and Ld is None and inpl == 64 and pl == 64 and e.use_halo and B >= e.halo_min_b and L1.wfF is not None \
+        if e.h16 and Ld is None and inpl == 64 and pl == 64 and e.use_halo and B >= e.halo_min_b and L1.wfF is not None \
                 and L1.wfmt.get("e", 1) == 1 and L2.wfmt.get("e", 1) == 1 and int(lib.gdrn_block64_eval_ok(B, Hc, Hc, e.dt)):
             # 64 channels (layer1): the whole BasicBlock as ONE launch, the intermediate in LDS (r6, csrc/block64.hip)
             f1, f2 = e.fold(pfx + ".bn1", L1), e.fold(pfx + ".bn2", L2)
@@ -858,12 +798,12 @@ class Plan:
             del self.tensors[pfx + ".raw1"], self.tensors[pfx + ".a1"], self.tensors[pfx + ".raw2"]
             return
         s2op = None
-        if Ld is not None and e.s2_halo and L1.wfF is not None:
+        if Ld is not None and e.h16 and L1.wfF is not None:
             # stage entry: conv1 (3x3 stride 2) and the 1x1 shortcut in ONE launch of the parity-plane kernel (r6), BatchNorms folded
             f1, fd = e.fold(pfx + ".bn1", L1), e.fold(pfx + ".downsample.1", Ld)
             self._hook_fold()
             res = self._E(B, Ho, Ho, pl)
-            s2op = self._s2(L1, x, inpl, a1, Hc, Ho, Ld=Ld, yd=res, bias=f1.shift, bias_d=fd.shift, act=1, evalw=True)
+            s2op = self._s2(L1, "e", x, a1, Hc, Ho, Ld=Ld, yd=res, bias=f1.shift, bias_d=fd.shift, act=1)
         if s2op is not None:
             self.fwd.append(s2op[0])
         else:
@@ -886,41 +826,37 @@ class Plan:
             # stage entry (r6): conv1 (3x3 stride 2) and the 1x1 shortcut conv in ONE launch of the parity-plane kernel, each with its
             # own BatchNorm-statistics rows
             rawd_ = E(B, Ho, Ho, pl)
-            s2op = self._s2(L1, x, inpl, raw1, Hc, Ho, Ld=Ld, yd=rawd_, stats=self.stats if S else None, stats_d=self.stats_b if S else None)
-        if s2op is not None:
-            op, cp, cpd_s2 = s2op
-        else:
-            op, cp = self._conv(L1, pend["x1"] if pend else x, inpl, raw1, Hc, Hc, Ho, Ho, stride, 1, stats=self.stats if S else None,
-                                xf=dict(pend["xf"], out=x) if pend else None)
+            s2op = self._s2(L1, "f", x, raw1, Hc, Ho, Ld=Ld, yd=rawd_, stats=self.stats if S else None, stats_d=self.stats_b if S else None)
+        op, rows1 = s2op or self._conv(L1, pend.x1 if pend else x, inpl, raw1, Hc, Hc, Ho, Ho, stride, 1, stats=self.stats if S else None,
+                                       xf=dict(pend.xf, out=x) if pend else None)
         self.fwd.append(op)
         xf1 = self._xf_ok(L2)  # bn1 + ReLU applied by conv2 on load (which also writes a1 for the weight gradient)
-        self.fwd += self._bn_fwd(pfx + ".bn1", raw1, cp, pl, npo, None if xf1 else a1)
-        s1 = self.bn[pfx + ".bn1"]
-        op, cp = self._conv(L2, raw1 if xf1 else a1, pl, raw2, Ho, Ho, Ho, Ho, 1, 1, stats=self.stats if S else None,
-                            xf=dict(mode=1, a=s1.scale, c=s1.shift, relu=True, out=a1) if xf1 else None)
+        self.fwd += self._bn_fwd(pfx + ".bn1", raw1, rows1, pl, npo, None if xf1 else a1)
+        op, rows2 = self._conv(L2, raw1 if xf1 else a1, pl, raw2, Ho, Ho, Ho, Ho, 1, 1, stats=self.stats if S else None,
+                               xf=_xf_bn_relu(self.bn[pfx + ".bn1"], out=a1) if xf1 else None)
         self.fwd.append(op)
         # block output relu(bn2(raw2) + identity): left to the next block's conv1 when that is a halo launch
         nxt1 = e.layers.get(f"backbone.layer{k.li}.{k.b + 1}.conv1")
         xf_out = nxt1 is not None and self._xf_ok(nxt1)
         if Ld is None:
-            self.fwd += self._bn_fwd(pfx + ".bn2", raw2, cp, pl, npo, None if xf_out else out, residual=x)
+            self.fwd += self._bn_fwd(pfx + ".bn2", raw2, rows2, pl, npo, None if xf_out else out, residual=x)
             s2 = self.bn[pfx + ".bn2"]
             # relu(scale2*raw2 + x + shift2)
-            return dict(x1=raw2, xf=dict(mode=2, x2=x, a=s2.scale, c=s2.shift, relu=True)) if xf_out else None
+            return _pend(raw2, dict(mode=2, x2=x, a=s2.scale, c=s2.shift, relu=True)) if xf_out else None
         k.rawd, idn = (rawd_ if s2op is not None else E(B, Ho, Ho, pl)), (None if xf_out else E(B, Ho, Ho, pl))
         self.tensors[pfx + ".rawd"] = k.rawd
         if idn is not None:
             self.tensors[pfx + ".idn"] = idn
-        self.fwd += self._bn_fwd(pfx + ".bn2", raw2, cp, pl, npo, None)
-        if s2op is not None:   # (the shortcut conv ran with conv1: only its BatchNorm's finalize is left, from its own rows)
-            self.fwd += self._bn_fwd(pfx + ".downsample.1", k.rawd, cpd_s2, pl, npo, idn, relu=0, stats=self.stats_b)
+        self.fwd += self._bn_fwd(pfx + ".bn2", raw2, rows2, pl, npo, None)
+        if s2op is not None:   # (the shortcut conv ran with conv1: only its BatchNorm's finalize is left, from its own rows -- as many as conv1's)
+            self.fwd += self._bn_fwd(pfx + ".downsample.1", k.rawd, rows1, pl, npo, idn, relu=0, stats=self.stats_b)
         else:
-            op, cpd = self._conv(Ld, x, inpl, k.rawd, Hc, Hc, Ho, Ho, stride, 0, stats=self.stats if S else None)
+            op, rows_d = self._conv(Ld, x, inpl, k.rawd, Hc, Hc, Ho, Ho, stride, 0, stats=self.stats if S else None)
             self.fwd.append(op)
-            self.fwd += self._bn_fwd(pfx + ".downsample.1", k.rawd, cpd, pl, npo, idn, relu=0)
+            self.fwd += self._bn_fwd(pfx + ".downsample.1", k.rawd, rows_d, pl, npo, idn, relu=0)
         s2, sd = self.bn[pfx + ".bn2"], self.bn[pfx + ".downsample.1"]
         if xf_out:   # relu(scale2*raw2 + scale_d*rawd + shift2 + shift_d)
-            return dict(x1=raw2, xf=dict(mode=2, x2=k.rawd, a=s2.scale, b=sd.scale, c=s2.shift, c2=sd.shift, relu=True))
+            return _pend(raw2, dict(mode=2, x2=k.rawd, a=s2.scale, b=sd.scale, c=s2.shift, c2=sd.shift, relu=True))
         self.fwd.append(_launch(e.lib.gdrn_bn_apply, "bn_apply", (raw2, s2.scale, s2.shift, idn, out, npo, pl, 1, e.dt)))
         return None
 
@@ -942,58 +878,46 @@ class Plan:
         xfb2 = pre2 and self._xf_ok(L2)
         need_dx = d_x is not None
         xfb1 = self._fusable(L2) and self._xf_ok(L1) and Ld is None and need_dx
-        xd2 = xd1 = None
-        if xfb2:
+        if pre2:
             g2 = d_out
-            grp, xd2 = self._bn_bwd(pfx + ".bn2", d_out, None, raw2, d_raw2, prereduced=True, xf=True)
-        elif pre2:
-            g2 = d_out
-            grp = self._bn_bwd(pfx + ".bn2", d_out, None, raw2, d_raw2, prereduced=True)
+            grp, xd2 = self._bn_bwd(pfx + ".bn2", d_out, None, raw2, d_raw2, sums="dgrad", xf=xfb2)
         else:
             g2 = E(B, Ho, Ho, pl)
             self.tensors[pfx + ".g2"] = g2
-            grp = self._bn_bwd(pfx + ".bn2", d_out, out, raw2, d_raw2, g_out=g2)
+            grp, xd2 = self._bn_bwd(pfx + ".bn2", d_out, out, raw2, d_raw2, g_out=g2)
         grp.append(self._wgrad(L2, a1, d_raw2, Ho, Ho, Ho, Ho, 1, 1, pl, pl, pl, pl))
         grp.append(self._unpack(L2))
         pre1 = self._fusable(L2)
-        op, _ = self._conv(L2, d_out if xfb2 else d_raw2, pl, d_a1, Ho, Ho, Ho, Ho, 1, 1, w=L2.wd, rows=L2.rows_d, cin=L2.cin_d, cout=pl,
-                           bnb=(pfx + ".bn1", raw1, None, True) if pre1 else None, xf=xd2)
-        grp.append(op)
-        if xfb1:
-            ops1, xd1 = self._bn_bwd(pfx + ".bn1", d_a1, a1, raw1, d_raw1, affine_mask=True, prereduced=True, xf=True)
-            grp += ops1
-        else:
-            grp += self._bn_bwd(pfx + ".bn1", d_a1, a1, raw1, d_raw1, affine_mask=True, prereduced=pre1)
+        grp.append(self._conv(L2, d_out if xfb2 else d_raw2, pl, d_a1, Ho, Ho, Ho, Ho, 1, 1, w=L2.wd, rows=L2.rows_d, cin=L2.cin_d, cout=pl,
+                              bnb=_bnb(pfx + ".bn1", raw1, affine=True) if pre1 else None, xf=xd2)[0])
+        ops1, xd1 = self._bn_bwd(pfx + ".bn1", d_a1, a1, raw1, d_raw1, affine_mask=True, sums="dgrad" if pre1 else "here", xf=xfb1)
+        grp += ops1
         grp.append(self._wgrad(L1, x, d_raw1, Hc, Hc, Ho, Ho, stride, 1, inpl, pl, inpl, pl))
         grp.append(self._unpack(L1))
         if Ld is not None:
             d_rawd, d_xd = E(B, Ho, Ho, pl), E(B, Hc, Hc, inpl)
             self.tensors.update({pfx + ".d_rawd": d_rawd, pfx + ".d_xd": d_xd})
-            grp += self._bn_bwd(pfx + ".downsample.1", g2, None, rawd, d_rawd)
+            grp += self._bn_bwd(pfx + ".downsample.1", g2, None, rawd, d_rawd)[0]
             grp.append(self._wgrad(Ld, x, d_rawd, Hc, Hc, Ho, Ho, stride, 0, inpl, pl, inpl, pl, defer=li >= 3))
             grp.append(self._unpack(Ld))
-            pbn = f"backbone.layer{li - 1}.{RESNET34_LAYERS[li - 2] - 1}.bn2"
+            # d_x = gradient w.r.t. the previous layer's last block output (mask = x): its bn2 backward is reduced by the launch that writes d_x
+            bnb = _bnb(f"backbone.layer{li - 1}.{RESNET34_LAYERS[li - 2] - 1}.bn2", prev_raw2, x) if e.gemm_bnb else None
             # (r6) conv1's data gradient, the shortcut conv's data gradient and the previous block's ReLU mask + bn2-backward sums as
             # ONE launch of the parity-class kernel: no d_xd tensor (three quarters zeros), no addend pass
-            s2d = self._s2d(L1, d_raw1, d_x, Ho, Hc, inpl, Ld=Ld, dyd=d_rawd, bnb=(pbn, prev_raw2, x)) if e.gemm_bnb else None
+            s2d = self._s2d(L1, "d", d_raw1, d_x, Ho, Hc, Ld=Ld, dyd=d_rawd, bnb=bnb) if bnb else None
             if s2d is not None:
-                grp.append(s2d)
+                grp.append(s2d[0])
                 del self.tensors[pfx + ".d_xd"]
             else:
-                op, _ = self._conv(Ld, d_rawd, pl, d_xd, Ho, Ho, Hc, Hc, 2, 0, mode=1, w=Ld.wd, rows=Ld.rows_d, cin=Ld.cin_d, cout=inpl)
-                grp.append(op)
-                # d_x = gradient w.r.t. the previous layer's last block output (mask = x): its bn2 backward is reduced here
-                op, _ = self._conv(L1, d_raw1, pl, d_x, Ho, Ho, Hc, Hc, 2, 1, mode=1, w=L1.wd, rows=L1.rows_d, cin=L1.cin_d,
-                                   cout=inpl, addend=d_xd, add_cs=inpl, bnb=(pbn, prev_raw2, x, False) if e.gemm_bnb else None)
-                grp.append(op)
+                grp.append(self._conv(Ld, d_rawd, pl, d_xd, Ho, Ho, Hc, Hc, 2, 0, mode=1, w=Ld.wd, rows=Ld.rows_d, cin=Ld.cin_d, cout=inpl)[0])
+                grp.append(self._conv(L1, d_raw1, pl, d_x, Ho, Ho, Hc, Hc, 2, 1, mode=1, w=L1.wd, rows=L1.rows_d, cin=L1.cin_d,
+                                      cout=inpl, addend=d_xd, add_cs=inpl, bnb=bnb)[0])
         elif need_dx:
             # previous block of the same layer: d_x is the gradient w.r.t. its output (mask = x, stored) and
             # feeds its bn2 backward (raw input prev_raw2)
             fuse_prev = b >= 1 and self._fusable(L1)
-            op, _ = self._conv(L1, d_a1 if xfb1 else d_raw1, pl, d_x, Ho, Ho, Hc, Hc, 1, 1, w=L1.wd, rows=L1.rows_d, cin=L1.cin_d, cout=inpl,
-                               addend=g2, add_cs=pl,
-                               bnb=(f"backbone.layer{li}.{b - 1}.bn2", prev_raw2, x, False) if fuse_prev else None, xf=xd1)
-            grp.append(op)
+            grp.append(self._conv(L1, d_a1 if xfb1 else d_raw1, pl, d_x, Ho, Ho, Hc, Hc, 1, 1, w=L1.wd, rows=L1.rows_d, cin=L1.cin_d, cout=inpl,
+                                  addend=g2, add_cs=pl, bnb=_bnb(f"backbone.layer{li}.{b - 1}.bn2", prev_raw2, x) if fuse_prev else None, xf=xd1)[0])
         self.bwd_groups.append(grp)
         c.d_x = d_out
 
@@ -1007,32 +931,32 @@ class Plan:
         xf_first = S and (not HEAD_CONVS[0][2]) and self._xf_ok(e.layers[h + str(HEAD_CONVS[0][0])])
         # (r6) the ConvTranspose's forward pass on the parity-class kernel (8 x 8 maps: two images per tile); the generic kernel keeps odd batch sizes
         if not S:
-            tf = self._convT_fwd(LT, h + "1", feat, h0, 8, 16, evalmode=True)
+            f = e.fold(h + "1", LT)
+            self._hook_fold()
+            tf = self._s2d(LT, "e", feat, h0, 8, 16, bias=f.shift, act=1)
             self.fwd.append(tf[0] if tf is not None else
                             self._conv_bn_eval(LT, h + "1", feat, 512, h0, 8, 8, 16, 16, 2, 1, relu=True, mode=1, cin=512, cout=256))
         else:
-            tf = self._convT_fwd(LT, h + "1", feat, rawt, 8, 16, stats=self.stats if S else None)
-            op, cp = tf if tf is not None else self._conv(LT, feat, 512, rawt, 8, 8, 16, 16, 2, 1, mode=1, cin=512, cout=256, stats=self.stats if S else None)
+            op, rows = self._s2d(LT, "f", feat, rawt, 8, 16, stats=self.stats) or \
+                self._conv(LT, feat, 512, rawt, 8, 8, 16, 16, 2, 1, mode=1, cin=512, cout=256, stats=self.stats)
             self.fwd.append(op)
-            self.fwd += self._bn_fwd(h + "1", rawt, cp, 256, B * 256, None if xf_first else h0)
+            self.fwd += self._bn_fwd(h + "1", rawt, rows, 256, B * 256, None if xf_first else h0)
         d_h0 = None
         if T:
             d_h0, d_rawt = E(B, 16, 16, 256), E(B, 16, 16, 256)
             self.tensors.update({h + "0.d_act": d_h0, h + "0.d_raw": d_rawt})
             pre_t = (not HEAD_CONVS[0][2]) and self._fusable(e.layers[h + str(HEAD_CONVS[0][0])])
-            grp = self._bn_bwd(h + "1", d_h0, h0, rawt, d_rawt, affine_mask=True, prereduced=pre_t)
+            grp = self._bn_bwd(h + "1", d_h0, h0, rawt, d_rawt, affine_mask=True, sums="dgrad" if pre_t else "here")[0]
             # ConvT weight grad = conv wgrad with roles swapped: "input" d_rawt (16x16, 256), "output grad" feat (8x8, 512)
             grp.append(self._wgrad(LT, d_rawt, feat, 16, 16, 8, 8, 2, 1, 256, 512, 256, 512))
             grp.append(self._unpack(LT))
             # (r6) the ConvTranspose's data gradient = a stride-2 conv of the output gradient: the parity-plane kernel with the BatchNorm-backward epilogue
-            op = self._convT_dgrad(LT, d_rawt, d_feat, 16, 8, ("backbone.layer4.2.bn2", prev_raw2, feat)) if e.gemm_bnb else None
-            if op is None:
-                op, _ = self._conv(LT, d_rawt, 256, d_feat, 16, 16, 8, 8, 2, 1, mode=0, w=LT.wd, rows=LT.rows_d, cin=256, cout=512,
-                                   bnb=("backbone.layer4.2.bn2", prev_raw2, feat, False) if e.gemm_bnb else None)
-            grp.append(op)
+            bnb = _bnb("backbone.layer4.2.bn2", prev_raw2, feat) if e.gemm_bnb else None
+            grp.append(((self._s2(LT, "d", d_rawt, d_feat, 16, 8, bnb=bnb) if bnb else None) or
+                        self._conv(LT, d_rawt, 256, d_feat, 16, 16, 8, 8, 2, 1, mode=0, w=LT.wd, rows=LT.rows_d, cin=256, cout=512, bnb=bnb))[0])
             self.bwd_groups.append(grp)
         # pend_h: hx = relu(bn(prev_raw)) is evaluated (and written to hx) by the next head conv while it stages its patch
-        pend_h = dict(x1=rawt, xf=dict(mode=1, a=self.bn[h + "1"].scale, c=self.bn[h + "1"].shift, relu=True)) if xf_first else None
+        pend_h = _pend(rawt, _xf_bn_relu(self.bn[h + "1"])) if xf_first else None
         return NS(hx=h0, d_hx=d_h0, Hh=16, prev_bn=h + "1", prev_raw=rawt, pend_h=pend_h, up_next=False)
 
     def _head_conv(self, c, hi):
@@ -1076,10 +1000,10 @@ class Plan:
         if not S:
             self.fwd.append(self._conv_bn_eval(Lc, h + str(bi), xin, 256, act, Hh, Hh, Hh, Hh, 1, 1, relu=True))
         else:
-            op, cp = self._conv(Lc, pend_h["x1"] if pend_h else xin, 256, raw, Hh, Hh, Hh, Hh, 1, 1, stats=self.stats if S else None,
-                                xf=dict(pend_h["xf"], out=xin) if pend_h else None)
+            op, rows = self._conv(Lc, pend_h.x1 if pend_h else xin, 256, raw, Hh, Hh, Hh, Hh, 1, 1, stats=self.stats,
+                                  xf=dict(pend_h.xf, out=xin) if pend_h else None)
             self.fwd.append(op)
-            self.fwd += self._bn_fwd(h + str(bi), raw, cp, 256, B * Hh * Hh, None if (xf_next or up_next) else act)
+            self.fwd += self._bn_fwd(h + str(bi), raw, rows, 256, B * Hh * Hh, None if (xf_next or up_next) else act)
         if not up_next:
             self.tensors[h + f"{ci}.act"] = act   # (behind a fused upsampling the activation is never stored)
         d_act = None
@@ -1090,23 +1014,19 @@ class Plan:
             # launch masks it and reduces this BN's backward sums
             pre = (not nxt[2] and self._fusable(e.layers[h + str(nxt[0])])) if nxt is not None else e.gemm_bnb  # (last conv: the 1x1 output conv's data gradient)
             xfb = self._xf_ok(Lc)  # this BN's backward apply inside Lc's data-gradient launch (mode 3, or 4 = with the ReLU mask)
-            xd = None
-            sd_ = bool(up_next and not pre)   # the fused upsampling's adjoint behind this conv has reduced this BatchNorm's backward sums
-            if xfb:
-                ops, xd = self._bn_bwd(h + str(bi), d_act, act, raw, d_raw, affine_mask=True, prereduced=pre, xf=True, sums_done=sd_)
-                grp += ops
-            else:
-                grp += self._bn_bwd(h + str(bi), d_act, act, raw, d_raw, affine_mask=True, prereduced=pre, sums_done=sd_)
+            # (behind a fused upsampling, that launch's adjoint has reduced this BatchNorm's backward sums)
+            ops, xd = self._bn_bwd(h + str(bi), d_act, act, raw, d_raw, affine_mask=True, xf=xfb,
+                                   sums="dgrad" if pre else ("upsample" if up_next else "here"))
+            grp += ops
             grp.append(self._wgrad(Lc, xin, d_raw, Hh, Hh, Hh, Hh, 1, 1, 256, 256, 256, 256))
             grp.append(self._unpack(Lc))
             fuse_in = (not up) and self._fusable(Lc)  # d_in is the gradient w.r.t. the previous BN+ReLU's output
-            op, _ = self._conv(Lc, d_act if xfb else d_raw, 256, d_in, Hh, Hh, Hh, Hh, 1, 1, w=Lc.wd, rows=Lc.rows_d, cin=256, cout=256,
-                               bnb=(prev_bn, prev_raw, None, True) if fuse_in else None, xf=xd)
-            grp.append(op)
+            grp.append(self._conv(Lc, d_act if xfb else d_raw, 256, d_in, Hh, Hh, Hh, Hh, 1, 1, w=Lc.wd, rows=Lc.rows_d, cin=256, cout=256,
+                                  bnb=_bnb(prev_bn, prev_raw, affine=True) if fuse_in else None, xf=xd)[0])
             if up_bwd is not None:
                 grp.append(up_bwd)
             self.bwd_groups.append(grp)
-        c.pend_h = dict(x1=raw, xf=dict(mode=1, a=self.bn[h + str(bi)].scale, c=self.bn[h + str(bi)].shift, relu=True)) if xf_next else None
+        c.pend_h = _pend(raw, _xf_bn_relu(self.bn[h + str(bi)])) if xf_next else None
         c.hx, c.d_hx, c.Hh, c.prev_bn, c.prev_raw, c.up_next = act, d_act, Hh, h + str(bi), raw, up_next
 
     def _head_out(self, c):
@@ -1125,8 +1045,7 @@ class Plan:
         # read them), but the forward pass does not read them back
         fused_tail = e.h16 and nreg == 64
         if not fused_tail:
-            op, _ = self._conv(LO, hx, 256, self.head_out, 64, 64, 64, 64, 1, 0, bias=bias_o, out_f32=1, y_cs=self.hs, cout=e.head_c)
-            self.fwd.append(op)
+            self.fwd.append(self._conv(LO, hx, 256, self.head_out, 64, 64, 64, 64, 1, 0, bias=bias_o, out_f32=1, y_cs=self.hs, cout=e.head_c)[0])
         self.pnp_in = e._zeros(M, 128)   # channels >= 5 + nreg stay zero (PREZEROED: the kernels do not re-write the pad)
         self.keep.append(self.pnp_in)
         self.tensors.update({"head_out": self.head_out, "pnp_in": self.pnp_in})
@@ -1186,22 +1105,13 @@ class Plan:
             # the 1x1 output conv's data gradient on its own kernel (K = 69: the generic 128 x 128 tile ran it at 83 TFLOP/s), with the ReLU mask and
             # the BatchNorm-backward sums of the head's last BatchNorm in the epilogue as the generic kernel's bnb_* epilogue has them
             sbp = self.bn[prev_bn]
-            nrows_h = int(lib.gdrn_head_out_dgrad_rows(B, 4096))
-            assert 0 < nrows_h and nrows_h * 2 * 256 <= self.stats.numel()
             head_dgrad = _launch(lib.gdrn_head_out_dgrad, "head_out_dgrad", (self.d_head, 128, LO.wd, LO.cin_d, prev_raw, 256, sbp.mean, sbp.invstd, sbp.scale,
-                                                                             sbp.shift, d_hx, 256, self.stats, B, 4096, e.dt))
-            coef_h = self._bn_coef_op(prev_bn, self.stats, nrows_h)
-
-            def op(st, ctx):
-                head_dgrad(st, ctx)
-                coef_h(st, ctx)
-
-            op.parts = (head_dgrad, coef_h)
-            op.meta = dict(kernel="head_out_dgrad64_kernel<bf16>", flops=2.0 * M * 256 * e.head_c, bytes=float(M * (128 + 256 + 256) * 2), layer=h + "23:dgrad")
+                                                                             sbp.shift, d_hx, 256, self.stats, B, 4096, e.dt),
+                                 self._meta("head_out_dgrad64_kernel<bf16>", self._macs(LO, 4096), M * (128 + 256 + 256) * 2, h + "23:dgrad"))
+            grp.append(self._with_coef(head_dgrad, prev_bn, int(lib.gdrn_head_out_dgrad_rows(B, 4096))))
         else:
-            op, _ = self._conv(LO, self.d_head, 128, d_hx, 64, 64, 64, 64, 1, 0, w=LO.wd, rows=LO.rows_d, cin=128, cout=256,
-                               bnb=(prev_bn, prev_raw, None, True) if e.gemm_bnb else None)
-        grp.append(op)
+            grp.append(self._conv(LO, self.d_head, 128, d_hx, 64, 64, 64, 64, 1, 0, w=LO.wd, rows=LO.rows_d, cin=128, cout=256,
+                                  bnb=_bnb(prev_bn, prev_raw, affine=True) if e.gemm_bnb else None)[0])
         self.bwd_groups.append(grp)
 
     def _pnp_conv(self, c, ci, gi):
@@ -1214,12 +1124,8 @@ class Plan:
         r, gact = E(B, Ho, Ho, 128), E(B, Ho, Ho, 128)
         mr = E(B, 32, 2, dtype=F32t)
         self.tensors.update({q + f"{ci}.raw": r, q + f"{ci}.act": gact})
-        s2op = self._s2(Lc, px, cin, r, Hp, Ho) if cin == Lc.cin_f else None   # (r6: the parity-plane kernel on the 64 -> 32 and 32 -> 16 convs)
-        if s2op is not None:
-            op = s2op[0]
-        else:
-            op, _ = self._conv(Lc, px, cin, r, Hp, Hp, Ho, Ho, 2, 1, cin=cin, cout=128)
-        self.fwd.append(op)
+        s2_ok = cin == Lc.cin_f   # (r6: the parity-plane / parity-class kernels where they cover the map)
+        self.fwd.append(((self._s2(Lc, "f", px, r, Hp, Ho) if s2_ok else None) or self._conv(Lc, px, cin, r, Hp, Hp, Ho, Ho, 2, 1, cin=cin, cout=128))[0])
         gam, bet = e.P[q + f"{gi}.weight"], e.P[q + f"{gi}.bias"]
         self.fwd.append(_launch(lib.gdrn_gn_relu_fwd, "gn_relu_fwd", (r, gam, bet, gact, mr, B, Ho * Ho, 128, 32, 1e-5, e.dt)))
         d_g = None
@@ -1232,10 +1138,8 @@ class Plan:
             self._zero_regions += [self._grad16(dgam), self._grad16(dbet)]
             grp.append(self._wgrad(Lc, px, d_r, Hp, Hp, Ho, Ho, 2, 1, cin, 128, cin, 128))
             grp.append(self._unpack(Lc))
-            op = self._s2d(Lc, d_r, d_px, Ho, Hp, cin) if cin == Lc.cin_f else None   # (r6: the parity-class kernel where it covers the map)
-            if op is None:
-                op, _ = self._conv(Lc, d_r, 128, d_px, Ho, Ho, Hp, Hp, 2, 1, mode=1, w=Lc.wd, rows=Lc.rows_d, cin=128, cout=cin)
-            grp.append(op)
+            grp.append(((self._s2d(Lc, "d", d_r, d_px, Ho, Hp) if s2_ok else None) or
+                        self._conv(Lc, d_r, 128, d_px, Ho, Ho, Hp, Hp, 2, 1, mode=1, w=Lc.wd, rows=Lc.rows_d, cin=128, cout=cin))[0])
             self.bwd_groups.append(grp)
         c.px, c.d_px, c.Hp, c.cin = gact, d_g, Ho, 128
 
@@ -1265,13 +1169,10 @@ class Plan:
                                     (f1, L2.wf, b2, f2, B, 1024, 256, 1024, 1024, 256, -1 if self.fc_tail else 2, ws2, e.dt),
                                     dict(kernel="linear_splitk_kernel", flops=2.0 * B * 1024 * 256, layer="pnp_net.fc2")))
         else:
-            op, _ = self._conv(L1, g2act, 128, f1, 8, 8, 1, 1, 1, 0, bias=b1, act=2, cin=128, cout=1024)
-            self.fwd.append(op)
-            op, _ = self._conv(L2, f1, 1024, f2, 1, 1, 1, 1, 1, 0, bias=b2, act=2, cin=1024, cout=256)
-            self.fwd.append(op)
+            self.fwd.append(self._conv(L1, g2act, 128, f1, 8, 8, 1, 1, 1, 0, bias=b1, act=2, cin=128, cout=1024)[0])
+            self.fwd.append(self._conv(L2, f1, 1024, f2, 1, 1, 1, 1, 1, 0, bias=b2, act=2, cin=1024, cout=256)[0])
         if self.fc_tail is None:
-            op, _ = self._conv(L3, f2, 256, self.fc_out, 1, 1, 1, 1, 1, 0, bias=e.rt_b, out_f32=1, cin=256, cout=9, y_cs=64)
-            self.fwd.append(op)
+            self.fwd.append(self._conv(L3, f2, 256, self.fc_out, 1, 1, 1, 1, 1, 0, bias=e.rt_b, out_f32=1, cin=256, cout=9, y_cs=64)[0])
         self._fc2 = (f2, b2, L3)
         return f1, f2
 
@@ -1305,14 +1206,12 @@ class Plan:
             self._unpack(L3),
             bias_grad(d_fc, 64, 9, self.rt_gb),   # = both .grad views
         ]
-        op, _ = self._conv(L3, d_fc, 64, d_f2, 1, 1, 1, 1, 1, 0, w=L3.wd, rows=L3.rows_d, cin=64, cout=256)
-        grp.append(op)
+        grp.append(self._conv(L3, d_fc, 64, d_f2, 1, 1, 1, 1, 1, 0, w=L3.wd, rows=L3.rows_d, cin=64, cout=256)[0])
         grp.append(_launch(lib.gdrn_leaky_bwd, "leaky_bwd", (d_f2, f2, d_f2p, B * 256, e.dt)))
         grp.append(self._wgrad(L2, f1, d_f2p, 1, 1, 1, 1, 1, 0, 1024, 256, 1024, 256, defer=True))
         grp.append(self._unpack(L2))
         grp.append(self._side(bias_grad(d_f2p, 256, 256, g_b2), defer=True))
-        op, _ = self._conv(L2, d_f2p, 256, d_f1, 1, 1, 1, 1, 1, 0, w=L2.wd, rows=L2.rows_d, cin=256, cout=1024)
-        grp.append(op)
+        grp.append(self._conv(L2, d_f2p, 256, d_f1, 1, 1, 1, 1, 1, 0, w=L2.wd, rows=L2.rows_d, cin=256, cout=1024)[0])
         grp.append(_launch(lib.gdrn_leaky_bwd, "leaky_bwd", (d_f1, f1, d_f1p, B * 1024, e.dt)))
         grp.append(self._wgrad(L1, g2act, d_f1p, 8, 8, 1, 1, 1, 0, 128, 1024, 128, 1024, defer=True))
         grp.append(self._unpack(L1))
@@ -1325,8 +1224,7 @@ class Plan:
             grp.append(_launch(lib.gdrn_linear_splitk, "linear_splitk fc1:dgrad", (d_f1p, L1.wd, None, d_g2, B, 1024, 8192, 1024, 1024, 8192, 0, ws1d, e.dt),
                                dict(kernel="linear_splitk_kernel", flops=2.0 * B * 8192 * 1024, layer="pnp_net.fc1:dgrad")))
         else:
-            op, _ = self._conv(L1, d_f1p, 1024, d_g2, 1, 1, 1, 1, 1, 0, w=L1.wd, rows=L1.rows_d, cin=1024, cout=8192, KH=1, KW=1, y_cs=8192)
-            grp.append(op)
+            grp.append(self._conv(L1, d_f1p, 1024, d_g2, 1, 1, 1, 1, 1, 0, w=L1.wd, rows=L1.rows_d, cin=1024, cout=8192, KH=1, KW=1, y_cs=8192)[0])
         self.bwd_groups.append(grp)
 
     def _pose(self):

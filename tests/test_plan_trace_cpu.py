@@ -85,7 +85,7 @@ def test_queries_that_pass_through_take_no_stream():
 def test_configurations_cover_every_engine_switch():
     """the grid the tool writes: 3 dtypes x 4 batch sizes x 4 modes, and one variant per environment switch that changes a launch list"""
     names = [c[0] for c in PT.CONFIGS]
-    assert len(names) == len(set(names)) == 48 + 13 + 1 + 2
+    assert len(names) == len(set(names)) == 48 + 11 + 2
     varied = {k for c in PT.CONFIGS for k in c[5]}
     src = open(os.path.join(ROOT, "gdr-net_amd", "engine.py")).read()
     read = set(re.findall(r'environ\.get\("(GDRN_[A-Z0-9_]+)"', src))

@@ -133,10 +133,9 @@ def _configs():
         for B in (3, 4, 64, 96):
             for tr, wl in ((True, True), (False, False), (False, True), (True, False)):
                 out.append((f"{dtype}_b{B}_{'T' if tr else 'F'}{'T' if wl else 'F'}", dtype, B, tr, wl, {}))
-    var = [("GDRN_V3", "0"), ("GDRN_V3", "2")] + [(k, "0") for k in ("GDRN_FUSE_XF", "GDRN_GEMM_BNB", "GDRN_FUSE_UP", "GDRN_S2_HALO", "GDRN_S2_TW8", "GDRN_FC_TAIL")]
+    var = [("GDRN_V3", "0"), ("GDRN_V3", "2")] + [(k, "0") for k in ("GDRN_FUSE_XF", "GDRN_GEMM_BNB", "GDRN_FUSE_UP", "GDRN_FC_TAIL")]
     var += [("GDRN_WGRAD_STREAM", "0"), ("GDRN_WGRAD_STREAM", "serial"), ("GDRN_BUCKETS", "5"), ("GDRN_HALO_WAVES", "4"), ("GDRN_HALO_WAVES", "8")]
     out += [(f"bf16_b64_TT_{k}={v}", "bf16", 64, True, True, {k: v}) for k, v in var]
-    out.append(("bf16_b64_FF_GDRN_BLOCK64=0", "bf16", 64, False, False, {"GDRN_BLOCK64": "0"}))
     out += [(f"fp32_b64_TT_GDRN_HALO_F32={v}", "fp32", 64, True, True, {"GDRN_HALO_F32": v}) for v in ("0", "1")]
     return out
 
