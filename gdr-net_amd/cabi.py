@@ -287,6 +287,7 @@ _SIGS = {
     "gdrn_scene_gt_visibility": [P, P, P, P, I, P, I, I, I, D, I, P, P, P, P, P, P, P, P, P],
     "gdrn_render_visibility": [P, P, P, P, P, P, I, I, P, P, P, P, P, I, I, I, D, D, P, P],
     "gdrn_shade_frames": [P, P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P],
+    "gdrn_shade_frames_tex": [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, I, I, P, P, P, P, P, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []

@@ -6,6 +6,9 @@ behind the xyz tool and the pose visualisation of ``core/utils/pose_utils.py``, 
 Two passes: ``render_visibility`` runs the depth rasterizer's walk with 64-bit keys (fp32 depth bits above the face index), ``render_frames``
 picks the nearest instance per frame pixel, recomputes that face's geometry in fp64 and shades it.  The rules are stated with the entry points
 in ``include/gdrn_hip.h``; what differs from the GL renderer is listed in INTEGRATION.md.  There is no CPU fallback.
+``render_frames_bop`` is the same render with the light model of the reference's second renderer, ``lib/pysixd/renderer_py.py`` (behind
+``renderer.create_renderer(..., mode="rgb")``): a UV texture map per class (``TexturedMeshTable``) instead of vertex colours where a model has
+one, Phong or flat shading, ``min(1, ambient + max(N.L, 0))`` without a specular term, bytes rounded half to even.
 
 Conventions: camera coordinates are OpenCV's (x right, y down, z forward), metres.  The reference's light is a position in GL eye space
 (x right, y up, z backward) for models in millimetres; ``from_gl_eye_mm`` converts.
@@ -153,16 +156,12 @@ def _per_frame(values, F, what, nonneg):
     return np.ascontiguousarray(a)
 
 
-def render_frames(table, labels, R, t, K, H, W, frame, num_frames=None, light=LIGHT, phong=PHONG, background=None, want_face=False,
-                  want_normals=False, near=render.NEAR, far=render.FAR):
-    """Shaded frames of N posed instances: instance i is the mesh ``labels[i]`` of the ``ShadedMeshTable`` ``table`` under ``R[i]``, ``t[i]`` seen
-    through ``K[i]`` ([3,3]: shared) in frame ``frame[i]`` -- poses and K device tensors as ``render.render_depth`` takes them, ``labels`` and
-    ``frame`` [N] from the host or the device, checked on the host.  ``num_frames``: F (default max(frame) + 1); a frame without instances is
-    its background.  ``light`` [3] or [F,3]: the light's position in camera coordinates, metres; ``phong`` [3] or [F,3]: (ambient, diffuse,
-    specular), finite and >= 0.  ``background`` [F,H,W,3] u8 device tensor or None (black).  Per pixel the nearest instance wins (the first in
-    input order among equal fp32 depths).  Returns a ``Frames``; nothing is read back."""
-    if not isinstance(table, ShadedMeshTable):
-        raise ValueError("render_frames needs a ShadedMeshTable (colours and normals per vertex)")
+
+
+def _render(table, labels, R, t, K, H, W, frame, num_frames, light, weights, background, want_face, want_normals, near, far, launch):
+    """The two-pass render behind ``render_frames`` and ``render_frames_bop``: argument checks, the visibility pass, the outputs, the CSR table and
+    the side tables.  ``weights(F)``: the per-frame fp64 host array that follows the lights in the fp64 side table.  ``launch(dev, vis, mesh, inst,
+    maps)`` makes the C call from the pointer groups of the shade entry points: the keys | verts .. colors | C .. W, light, weights | background .. stream."""
     H, W = int(H), int(W)
     if H < 1 or W < 1:
         raise ValueError("H and W: at least one pixel")
@@ -179,7 +178,7 @@ def render_frames(table, labels, R, t, K, H, W, frame, num_frames=None, light=LI
         if F < 0:
             raise ValueError("num_frames: not negative")
         fr_host = devargs.index_vector(frame, N, F, dev, "frame")[1]
-    light, phong = _per_frame(light, F, "light", False), _per_frame(phong, F, "phong", True)
+    light, weights = _per_frame(light, F, "light", False), weights(F)
     if background is not None:
         background = devargs.device_tensor(background, None, None, "background", WHERE)
         if background.dtype != torch.uint8 or tuple(background.shape) != (F, H, W, 3):
@@ -195,14 +194,159 @@ def render_frames(table, labels, R, t, K, H, W, frame, num_frames=None, light=LI
         return out
     off_host, inst_host = csr_of_frames(fr_host, F)
     ints = torch.from_numpy(np.concatenate([off_host, inst_host])).to(dev)                # one upload each of the integer
-    reals = torch.from_numpy(np.concatenate([light.ravel(), phong.ravel()])).to(dev)      # and the fp64 side tables
+    reals = torch.from_numpy(np.concatenate([light.ravel(), weights.ravel()])).to(dev)    # and the fp64 side tables
     tb, p = table.on(dev), cabi.ptr
-    cabi.check(cabi.load().gdrn_shade_frames(p(vis), p(tb["verts"]), p(tb["faces"]), p(tb["vert_off"]), p(tb["nverts"]), p(tb["face_off"]),
-                                             p(tb["nfaces"]), p(tb["normals"]), p(tb["colors"]), table.num_classes, p(lab), lab_host.ctypes.data,
-                                             p(R), p(t), p(K), p(ints), off_host.ctypes.data, p(ints[F + 1:]), inst_host.ctypes.data, F, N, H, W,
-                                             p(reals), p(reals[3 * F:]), p(background), p(out.rgb), p(out.depth), p(out.index), p(out.face),
-                                             p(out.normals), devargs.stream(dev)), "shade_frames")
+    mesh = [p(tb[k]) for k in ("verts", "faces", "vert_off", "nverts", "face_off", "nfaces", "normals", "colors")]
+    inst = (table.num_classes, p(lab), lab_host.ctypes.data, p(R), p(t), p(K), p(ints), off_host.ctypes.data, p(ints[F + 1:]), inst_host.ctypes.data,
+            F, N, H, W, p(reals), p(reals[3 * F:]))
+    maps = (p(background), p(out.rgb), p(out.depth), p(out.index), p(out.face), p(out.normals), devargs.stream(dev))
+    launch(dev, p(vis), mesh, inst, maps)
     return out
+
+
+def render_frames(table, labels, R, t, K, H, W, frame, num_frames=None, light=LIGHT, phong=PHONG, background=None, want_face=False,
+                  want_normals=False, near=render.NEAR, far=render.FAR):
+    """Shaded frames of N posed instances: instance i is the mesh ``labels[i]`` of the ``ShadedMeshTable`` ``table`` under ``R[i]``, ``t[i]`` seen
+    through ``K[i]`` ([3,3]: shared) in frame ``frame[i]`` -- poses and K device tensors as ``render.render_depth`` takes them, ``labels`` and
+    ``frame`` [N] from the host or the device, checked on the host.  ``num_frames``: F (default max(frame) + 1); a frame without instances is
+    its background.  ``light`` [3] or [F,3]: the light's position in camera coordinates, metres; ``phong`` [3] or [F,3]: (ambient, diffuse,
+    specular), finite and >= 0.  ``background`` [F,H,W,3] u8 device tensor or None (black).  Per pixel the nearest instance wins (the first in
+    input order among equal fp32 depths).  Returns a ``Frames``; nothing is read back."""
+    if not isinstance(table, ShadedMeshTable):
+        raise ValueError("render_frames needs a ShadedMeshTable (colours and normals per vertex)")
+
+    def launch(dev, vis, mesh, inst, maps):
+        cabi.check(cabi.load().gdrn_shade_frames(vis, *mesh, *inst, *maps), "shade_frames")
+
+    return _render(table, labels, R, t, K, H, W, frame, num_frames, light, lambda F: _per_frame(phong, F, "phong", True), background, want_face,
+                   want_normals, near, far, launch)
+
+
+# ---- the BOP renderer's light model: UV textures, flat shading (lib/pysixd/renderer_py.py) ----
+AMBIENT = 0.5                # renderer.py:24-28: the default ambient weight; the default light sits at the camera origin
+GRAY = 0.5                   # a model without colours is drawn gray (renderer_py.py:348-350)
+TEX_MAX_SIDE = 16384         # GDRN_TEX_MAX_SIDE
+SHADINGS = {"phong": 0, "flat": 1}         # GDRN_SHADING_*
+FILTERS = {"nearest": 0, "bilinear": 1}    # GDRN_TEXFILTER_*
+
+
+def pack_texels(image):
+    """[h,w,3] u8 -> [h*w] uint32, one texel per dword as c0 | c1 << 8 | c2 << 16, rows in the order given"""
+    t = image.astype(np.uint32)
+    return (t[..., 0] | (t[..., 1] << 8) | (t[..., 2] << 16)).reshape(-1)
+
+
+class TexturedMeshTable(ShadedMeshTable):
+    """A ``ShadedMeshTable`` with UV coordinates per vertex and one texture map per class, what ``inout.load_ply`` gives for a BOP model that names a
+    texture file: everything that takes a MeshTable or a ShadedMeshTable takes it unchanged (``render_frames`` draws its vertex colours).
+    ``colors_list``: as ShadedMeshTable; ``None`` (for the list or for one class) is 0.5 gray, as the reference draws a model without colours.
+    ``textures[c]``: None, or the decoded image [h,w,3] as u8 or as floats in [0, 1] (rounded to u8 with rint), rows in FILE order (row 0 = the
+    top) -- NOT flipped by the caller -- channels in any order: ``render_frames_bop`` writes the same order.  ``uv_list[c]``: [n_c,2], finite,
+    required where a texture is given (v = 0 is the bottom row of the image); zeros elsewhere.  ``uvs`` [sum n_c,2] fp64, ``texels`` uint32 (one
+    texel per dword), ``tex`` [C,3] int32 = (offset, h, w), h = 0 without a texture.  Wrong shapes, non-finite UVs, a texture side outside
+    [1, 16384] or 2^31 texels and more raise ValueError."""
+
+    TABLES = ShadedMeshTable.TABLES + ("uvs", "texels", "tex")
+
+    def __init__(self, vertices_list, faces_list, colors_list=None, normals_list=None, uv_list=None, textures=None, device=None):
+        C = len(vertices_list)
+        for name, lst in (("colors_list", colors_list), ("uv_list", uv_list), ("textures", textures)):
+            if lst is not None and len(lst) != C:
+                raise ValueError(f"{name} needs one entry per class")
+        nv = [np.asarray(v).reshape(-1, 3).shape[0] for v in vertices_list]
+        colors_list = [None] * C if colors_list is None else list(colors_list)
+        colors_list = [np.full((nv[c], 3), GRAY) if col is None else col for c, col in enumerate(colors_list)]
+        super().__init__(vertices_list, faces_list, colors_list, normals_list)
+        uvs, texels, tex, total = [], [], np.zeros((C, 3), dtype=np.int32), 0
+        for c in range(C):
+            n = int(self.nverts[c])
+            image = None if textures is None else textures[c]
+            uv = None if uv_list is None else uv_list[c]
+            if uv is None:
+                if image is not None:
+                    raise ValueError(f"class {c} has a texture and no UV coordinates")
+                uv = np.zeros((n, 2))
+            uv = np.asarray(uv)
+            if uv.shape != (n, 2) or not (np.issubdtype(uv.dtype, np.floating) or np.issubdtype(uv.dtype, np.integer)):
+                raise ValueError(f"UV coordinates of class {c}: [{n}, 2] numbers, one pair per vertex")
+            uv = uv.astype(np.float64)
+            if not np.all(np.isfinite(uv)):
+                raise ValueError(f"UV coordinates of class {c}: finite")
+            uvs.append(uv)
+            if image is None:
+                continue
+            image = np.asarray(image)
+            if image.ndim != 3 or image.shape[2] != 3:
+                raise ValueError(f"texture of class {c}: [h, w, 3]")
+            h, w = image.shape[:2]
+            if not (1 <= h <= TEX_MAX_SIDE and 1 <= w <= TEX_MAX_SIDE):
+                raise ValueError(f"texture of class {c}: sides within [1, {TEX_MAX_SIDE}]")
+            if np.issubdtype(image.dtype, np.floating):
+                if not np.all(np.isfinite(image)) or image.min() < 0.0 or image.max() > 1.0:
+                    raise ValueError(f"texture of class {c}: floats in [0, 1]")
+                image = np.rint(255.0 * image.astype(np.float64)).astype(np.uint8)
+            elif image.dtype != np.uint8:
+                raise ValueError(f"texture of class {c}: u8 or floats in [0, 1]")
+            tex[c] = (total, h, w)
+            total += h * w
+            if total >= 2 ** 31:
+                raise ValueError("the texel table is indexed with int32 offsets")
+            texels.append(pack_texels(image))
+        self.uvs = np.ascontiguousarray(np.concatenate(uvs, axis=0))
+        self.texels = np.ascontiguousarray(np.concatenate(texels)) if texels else np.zeros(0, dtype=np.uint32)
+        self.tex = tex
+        if device is not None:
+            self.on(device)
+
+
+def _texture_tables(table, dev):
+    """(uvs, texels, tex on the device, tex on the host, n_texels) of a table; a plain ShadedMeshTable counts as untextured everywhere: zero UVs
+    and an all-zero ``tex``, kept with the table's device copies"""
+    if isinstance(table, TexturedMeshTable):
+        tb = table.on(dev)
+        return tb["uvs"], tb["texels"], tb["tex"], table.tex, int(table.texels.size)
+    table.on(dev)
+    cache = table.__dict__["_dev"].setdefault("untextured/" + str(dev), {})
+    if not cache:
+        cache.update(uvs=torch.zeros(int(table.verts.shape[0]), 2, dtype=torch.float64, device=dev),
+                     tex=torch.zeros(table.num_classes, 3, dtype=torch.int32, device=dev), tex_host=np.zeros((table.num_classes, 3), dtype=np.int32))
+    return cache["uvs"], None, cache["tex"], cache["tex_host"], 0
+
+
+def render_frames_bop(table, labels, R, t, K, H, W, frame, num_frames=None, light=(0.0, 0.0, 0.0), ambient=AMBIENT, shading="phong",
+                      filter="nearest", background=None, want_face=False, want_normals=False, near=render.NEAR, far=render.FAR):
+    """Frames of N posed instances with the light model of the reference's BOP renderer (``lib/pysixd/renderer_py.py``, ``mode="rgb"``): the
+    arguments, the visibility pass and the returned ``Frames`` of ``render_frames``, with another shading rule.  A class of a
+    ``TexturedMeshTable`` that has a texture takes its base colour from the texture at the interpolated UV coordinates, every other class (and
+    every class of a plain ``ShadedMeshTable``) from its vertex colours.  ``ambient``: a number or [F], finite and >= 0 (the reference's default
+    0.5); ``light`` [3] or [F,3], camera coordinates in metres (default: the camera origin).  The pixel is ``round(255 min(1, ambient + max(N.L, 0))
+    colour)``, half to even, without a specular term.  ``shading``: "phong" (interpolated vertex normals) or "flat" (the face normal, turned
+    towards the camera).  ``filter``: "nearest" (the default) or "bilinear", both with clamp-to-edge and without mipmaps -- which of the two the
+    reference's GL texture uses could not be established, so both exist.  ``Frames.normals`` reports the normal that was used."""
+    if not isinstance(table, ShadedMeshTable):
+        raise ValueError("render_frames_bop needs a ShadedMeshTable or a TexturedMeshTable")
+    if shading not in SHADINGS or filter not in FILTERS:
+        raise ValueError(f"shading: one of {sorted(SHADINGS)}; filter: one of {sorted(FILTERS)}")
+
+    def weights(F):
+        a = ambient.detach().cpu().numpy() if isinstance(ambient, torch.Tensor) else np.asarray(ambient)
+        try:
+            a = a.astype(np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("ambient: a number or [F] numbers") from None
+        if a.shape == ():
+            a = np.broadcast_to(a, (F,))
+        if a.shape != (F,) or not np.all(np.isfinite(a)) or (a.size and a.min() < 0.0):
+            raise ValueError(f"ambient: a number or [{F}], finite and not negative")
+        return np.ascontiguousarray(a)
+
+    def launch(dev, vis, mesh, inst, maps):
+        uvs, texels, tex, tex_host, n_texels = _texture_tables(table, dev)
+        p = cabi.ptr
+        cabi.check(cabi.load().gdrn_shade_frames_tex(vis, *mesh, p(uvs), p(texels), p(tex), tex_host.ctypes.data, n_texels, *inst, SHADINGS[shading],
+                                                     FILTERS[filter], *maps), "shade_frames_tex")
+
+    return _render(table, labels, R, t, K, H, W, frame, num_frames, light, weights, background, want_face, want_normals, near, far, launch)
 
 
 def random_lights(F, rng, phong=PHONG):

@@ -1117,6 +1117,55 @@ int gdrn_shade_frames(const unsigned long long* vis, const double* verts, const 
                       const unsigned char* background, unsigned char* rgb, float* depth, int* index, int* face, unsigned char* normal_map,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Textured and flat-shaded frames with the BOP renderer's light model (added within ABI 5: a new entry point, nothing changed): what the reference
+ * draws with lib/pysixd/renderer_py.py (renderer.create_renderer(..., mode="rgb")) -- a UV texture map instead of vertex colours where the model
+ * has one, Phong or flat shading, light_w = min(1, ambient_w + max(L.N, 0)) without a specular term, np.round as the last step.
+ *
+ * gdrn_shade_frames_tex: the second pass of gdrn_shade_frames with another shading rule: the same arguments, the same launch (one thread per frame
+ *   pixel), the same CSR table and host copies, and in addition
+ *     uvs [sum nverts][2] fp64, packed like verts: the texture coordinates of every vertex (zeros for a class without a texture);
+ *     texels [n_texels] uint32, one texel per dword as c0 | c1 << 8 | c2 << 16 in the channel order given (that of the colour table), the rows of
+ *       a texture in FILE order: row 0 = the top of the image.  One texel is one aligned 4-byte load; nullable when n_texels == 0;
+ *     tex [C][3] int32 = (offset into texels, h, w) per class, h == 0: the class has no texture;  tex_host: its host copy, checked before the
+ *       launch: offset >= 0, offset + h w <= n_texels, h and w both 0 or both in [1, GDRN_TEX_MAX_SIDE];
+ *     ambient [F] fp64, the ambient weight per frame;  light [F][3] fp64 as for gdrn_shade_frames (the reference's default: the camera origin);
+ *     shading: GDRN_SHADING_PHONG or GDRN_SHADING_FLAT;  filter: GDRN_TEXFILTER_NEAREST or GDRN_TEXFILTER_BILINEAR; both uniform per call.
+ *   Per pixel, everything fp64, contraction off, every fused operation an explicit fma():
+ *     instance, geometry, weights   exactly those of gdrn_shade_frames (the same device functions): depth, index and face of the two entry points
+ *                    are bit-identical on the same vis.  wa, wb, wc: the weights of a, b, c;  n = (b - a) x (c - a) of the sorted vertices, d the ray
+ *     uv             u = fma(wa, u_a, fma(wb, u_b, wc u_c)), v likewise: the nesting of the interpolated colour
+ *     normal N       GDRN_SHADING_PHONG: normalize(R n_interp), as gdrn_shade_frames.  GDRN_SHADING_FLAT: normalize(n) of the camera-space face
+ *                    normal, negated when n.d > 0 so that it faces the camera (N.d <= 0) -- what cross(dFdx(v_eye_pos), dFdy(v_eye_pos)) gives
+ *                    for either winding (renderer_py.py:66).  The zero vector if the length is 0.
+ *     light          L = normalize(light - P);  diff = max(N.L, 0);  lw = min(1, ambient + diff)   (renderer_py.py:94-96)
+ *     base colour    a class with a texture: the sampled texel / 255, vertex colours ignored (renderer_py.py:98-99); otherwise the interpolated
+ *                    vertex colour fma(wa, c_a, fma(wb, c_b, wc c_c))
+ *     nearest        i = clamp(floor(u w), 0, w - 1), j = clamp(floor(v h), 0, h - 1), the texel of file row h - 1 - j, column i:
+ *                    v = 0 is the bottom row (the reference flips the image before the upload) and coordinates outside [0, 1] take the edge
+ *                    texel (GL's clamp-to-edge).  The clamp is done in fp64 before the conversion to int: no |u| overflows it
+ *     bilinear       x = u w - 0.5 (a product and a difference, not fused), i0 = floor(x), fx = x - i0, columns clamp(i0) and clamp(i0 + 1) in
+ *                    [0, w - 1]; y = v h - 0.5, j0, fy and the rows h - 1 - clamp(j0), h - 1 - clamp(j0 + 1) likewise (clamp-to-edge); per channel
+ *                    on the byte values  lo = fma(fx, t10 - t00, t00), hi = fma(fx, t11 - t01, t01), c = fma(fy, hi - lo, lo) / 255
+ *                    (t00 = row of j0, column i0; t10 = row of j0, column i0 + 1; t01, t11 = the row of j0 + 1): x first, then y.  No mipmaps
+ *     output         q_k = rint(255 (lw c_k)), round-half-to-even (np.round, renderer_py.py:506), clamped into the byte -- NOT the
+ *                    floor(255 rgb_k + 0.5) of gdrn_shade_frames
+ *   normal_map reports the N that was used, quantised as gdrn_shade_frames does: floor(255 (0.5 N + 0.5) + 0.5).  rgb, depth, index, face, the
+ *   background, empty pixels and frames, N == 0, the 4-byte alignment of the byte maps: as gdrn_shade_frames.
+ * Status: as gdrn_shade_frames, and GDRN_ERR_ARG for uvs, tex or tex_host NULL, texels NULL with n_texels > 0, n_texels < 0, a tex_host row that
+ *   breaks the rule above, an unknown shading or filter.  Everything is checked on the host before a stream or a device pointer is touched.  No
+ *   scratch memory, no atomics, no read-back: repeated calls give the same bits. */
+enum { GDRN_SHADING_PHONG = 0, GDRN_SHADING_FLAT = 1 };
+enum { GDRN_TEXFILTER_NEAREST = 0, GDRN_TEXFILTER_BILINEAR = 1 };
+enum { GDRN_TEX_MAX_SIDE = 16384 };
+int gdrn_shade_frames_tex(const unsigned long long* vis, const double* verts, const int* faces, const int* vert_off, const int* nverts,
+                          const int* face_off, const int* nfaces, const double* normals, const double* colors, const double* uvs,
+                          const unsigned int* texels, const int* tex, const int* tex_host, int n_texels, int C, const int* labels,
+                          const int* labels_host, const double* R, const double* t, const double* K, const int* inst_off, const int* inst_off_host,
+                          const int* inst, const int* inst_host, int F, int N, int H, int W, const double* light, const double* ambient, int shading,
+                          int filter, const unsigned char* background, unsigned char* rgb, float* depth, int* index, int* face,
+                          unsigned char* normal_map, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
