@@ -288,12 +288,15 @@ _SIGS = {
     "gdrn_render_visibility": [P, P, P, P, P, P, I, I, P, P, P, P, P, I, I, I, D, D, P, P],
     "gdrn_shade_frames": [P, P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P],
     "gdrn_shade_frames_tex": [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, I, I, P, P, P, P, P, P, P],
+    "gdrn_cou_maps_workspace_bytes": [I],
+    "gdrn_cou_maps": [P, P, I, I, I, I, P, P, P, P, P],
+    "gdrn_cou_bb": [P, P, I, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []
 _RET_LL = ("gdrn_workspace_bytes", "gdrn_pose_metrics_workspace_bytes", "gdrn_pnp_workspace_bytes", "gdrn_vsd_workspace_bytes",
            "gdrn_mssd_mspd_workspace_bytes", "gdrn_model_prep_workspace_bytes", "gdrn_ad_errors_workspace_bytes",
-           "gdrn_sym_errors_workspace_bytes")
+           "gdrn_sym_errors_workspace_bytes", "gdrn_cou_maps_workspace_bytes")
 EXPORTS = tuple(_SIGS.keys())
 _libs = {}
 

@@ -736,6 +736,86 @@ def bop_test_depth(inp, depth_gt):
 
 
 # ----------------------------------------------------------------------------------------------
+# scenes of the complement-over-union errors (gdrnet_amd.cou_metrics, golden G19)
+# ----------------------------------------------------------------------------------------------
+COU_SEEDS = {"cus": 211}
+# ^ the seed golden G19 was drawn with (tests/golden/make_golden_g19.py moves on while a required row is missing, a pixel centre of a render lies
+#   within 1e-6 px of a triangle edge or a cus sits within 1e-6 of the 0.5 threshold)
+COU_ROWS = {"exact": 0, "off_object": 1, "est_outside": 2, "both_empty": 3, "cut_left": 4, "cut_right": 5, "cut_top": 6, "cut_bottom": 7}
+COU_GRADED = (8, 9, 10, 11, 12, 13)          # est = gt shifted across the image plane by COU_SHIFTS of the object's size, slightly rotated
+COU_SHIFTS = (0.17, 0.24, 0.3, 0.44, 0.52, 0.6)
+# x, y, w, h pairs for cou_bb: identical | disjoint | touching along a vertical edge (w_inter == 0) | touching along a horizontal edge | touching
+# in a corner | contained | containing | zero-area est | zero-area both at one place | partial overlap | the same shifted into negative
+# coordinates | fractional overlap | fractional touching | fractional contained | a one-pixel box inside | large coordinates
+COU_BB_PAIRS = (
+    ((3, 4, 10, 6), (3, 4, 10, 6)), ((0, 0, 5, 5), (20, 30, 4, 4)), ((0, 0, 5, 5), (5, 0, 5, 5)), ((2, 1, 6, 3), (2, 4, 6, 7)),
+    ((0, 0, 5, 5), (5, 5, 2, 2)), ((4, 4, 3, 2), (0, 0, 20, 10)), ((0, 0, 20, 10), (4, 4, 3, 2)), ((3, 3, 0, 4), (0, 0, 10, 10)),
+    ((5, 5, 0, 0), (5, 5, 0, 0)), ((0, 0, 10, 10), (5, 7, 10, 10)), ((-8, -9, 10, 10), (-3, -2, 10, 10)), ((0.5, 0.25, 3.75, 2.5), (1.125, 1.0, 4.3, 2.2)),
+    ((0.1, 0.2, 0.7, 0.3), (0.8, 0.2, 0.9, 0.3)), ((1.3, 1.7, 0.9, 1.1), (0.2, 0.4, 7.7, 5.9)), ((7, 3, 1, 1), (5, 2, 6, 4)),
+    ((100000, 200000, 3000, 1000), (101000, 200500, 3000, 1000)),
+)
+
+
+def make_cou_inputs(case, seed=None):
+    """Inputs of the complement-over-union golden G19 (gdrnet_amd.cou_metrics against lib/pysixd/pose_error.py cus / cou_mask / cou_bb), fp64, metres.
+
+    "cus"  14 rows in frames of 47 x 61 (H * W = 2867 is odd: a row's slice of the batch starts at any alignment) over the three mesh classes of
+           make_bop_metric_inputs("vsd") -- 0: a 0.1 m cube, 1: the perturbed icosphere, 2: a 0.12 x 0.09 m rectangle -- with a skew-free K per
+           row (rows 10 and up have another camera).  Rows (COU_ROWS): 0 est = gt exactly | 1 est shifted off the object, both in view
+           (intersection 0) | 2 est outside the frame | 3 gt outside the frame and est behind the near plane (union 0) | 4 .. 7 the est
+           silhouette cut by the left, right, top, bottom frame edge | COU_GRADED: est = gt rotated by 2 .. 8 degrees and shifted across the
+           image plane by COU_SHIFTS of the object's apparent size, so that cus falls on both sides of its 0.5 threshold."""
+    if case != "cus":
+        raise ValueError(case)
+    seed = COU_SEEDS[case] if seed is None else seed
+    u = lambda tag, *shape: hash_uniform(seed, tag, shape)  # noqa: E731
+    H, W, N = 47, 61, 14
+    rv, rf = mesh_rectangle(8, 8)
+    meshes = [mesh_cube(0.1), mesh_icosphere(3, 0.05, 0.35, seed), (rv * np.array([0.12, 0.09, 1.0]), rf)]
+    size = np.array([0.1, 0.1, 0.09])               # the extent a shift is measured in, per class
+    labels = np.arange(N, dtype=np.int64) % 3
+    K1 = np.array([[70.0, 0.0, 30.3], [0.0, 71.0, 23.4], [0.0, 0.0, 1.0]])
+    K2 = np.array([[64.5, 0.0, 29.1], [0.0, 63.0, 22.2], [0.0, 0.0, 1.0]])
+    K = np.stack([K2 if i >= 10 else K1 for i in range(N)])
+    R_gt = _random_rotations(seed, "R_gt", N)
+    for i in range(N):
+        if labels[i] == 2:   # the rectangle: roughly facing the camera
+            ax = hash_normal(seed, f"tilt{i}", (1, 3))
+            R_gt[i] = _axis_angle(ax / np.linalg.norm(ax), np.array([25.0]))[0]
+    z = 0.42 + 0.1 * u("t_z", N)
+    centre = np.array([30.0, 23.0]) + 6.0 * (u("t_px", N, 2) - 0.5)
+
+    def at(i, px):   # the translation that puts the model origin of row i on pixel px at depth z[i]
+        return np.array([(px[0] - K[i, 0, 2]) / K[i, 0, 0] * z[i], (px[1] - K[i, 1, 2]) / K[i, 1, 1] * z[i], z[i]])
+
+    t_gt = np.stack([at(i, centre[i]) for i in range(N)])
+    ang = 2.0 + 6.0 * u("ang", N)
+    axis = hash_normal(seed, "axis", (N, 3))
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    R_est = _axis_angle(axis, ang) @ R_gt
+    t_est = t_gt + 0.004 * (u("t_jit", N, 3) - 0.5)
+    r = COU_ROWS
+    R_est[r["exact"]], t_est[r["exact"]] = R_gt[r["exact"]], t_gt[r["exact"]]
+    i = r["off_object"]
+    t_gt[i], t_est[i] = at(i, (14.0, 22.0)), at(i, (46.0, 25.0))
+    t_est[r["est_outside"]] = t_gt[r["est_outside"]] + np.array([2.0, 0.0, 0.0])
+    i = r["both_empty"]
+    t_gt[i], t_est[i] = t_gt[i] + np.array([0.0, -2.0, 0.0]), t_gt[i] * np.array([1.0, 1.0, -1.0])
+    for name, px, inward in (("cut_left", (2.0, 20.0), (10.0, 1.0)), ("cut_right", (58.5, 27.0), (-10.0, -1.0)), ("cut_top", (25.0, 1.5), (1.0, 14.0)),
+                             ("cut_bottom", (35.0, 44.5), (-1.0, -10.0))):
+        i = r[name]
+        jit = u(f"cut_{name}", 2) - 0.5
+        t_est[i] = at(i, np.array(px) + jit)
+        t_gt[i] = at(i, np.array(px) + jit + np.array(inward))
+    for i, s in zip(COU_GRADED, COU_SHIFTS):
+        th = 2.0 * np.pi * u(f"dir{i}", 1)[0]
+        t_est[i] = t_gt[i] + s * size[labels[i]] * np.array([np.cos(th), np.sin(th), 0.0])
+    return dict(vertices=[m[0] for m in meshes], faces=[m[1] for m in meshes], labels=labels, obj_names=["cube", "blob", "card"], R_est=R_est,
+                t_est=t_est, R_gt=R_gt, t_gt=t_gt, K=K, H=H, W=W, near=0.01, far=6.5, rows=dict(COU_ROWS), graded=COU_GRADED,
+                bb_pairs=np.array(COU_BB_PAIRS, dtype=np.float64), seed=seed)
+
+
+# ----------------------------------------------------------------------------------------------
 # estimates of the YCB-V score tables (gdrnet_amd.sixd_scores, golden G18)
 # ----------------------------------------------------------------------------------------------
 SIXD_SCORE_SEEDS = {"sym": 191}

@@ -1166,6 +1166,39 @@ int gdrn_shade_frames_tex(const unsigned long long* vis, const double* verts, co
                           int filter, const unsigned char* background, unsigned char* rgb, float* depth, int* index, int* face,
                           unsigned char* normal_map, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Complement-over-union pose errors on the device (added within ABI 5: new entry points, nothing changed): the error types cus, cou_mask, cou_bb
+ * and cou_bb_proj of lib/pysixd/pose_error.py:466-589 for N estimates per call.  Counts and bounds are integers, reduced with integer atomics
+ * only: the result does not depend on the launch shape or on any order, repeated calls give the same bits, and a row's result does not depend on
+ * the other rows of the call.
+ *
+ * gdrn_cou_maps: est, gt [N][H][W], the silhouette under the estimated and the ground-truth pose, both of the element kind `kind`:
+ *     GDRN_COU_DEPTH  fp32 (gdrn_render_depth's maps or any other): a pixel is covered iff value > 0 as IEEE compares fp32 -- NaN, -0.0, 0.0 and
+ *                     negatives are not covered, +inf and subnormals are.  Decided on the bit pattern (0x00000001 .. 0x7f800000): no denormal
+ *                     mode enters.  (pose_error.cus: depth > 0)
+ *     GDRN_COU_MASK   one byte per pixel (uint8 or bool storage): covered iff the byte is non-zero.  (pose_error.cou_mask: astype(bool))
+ *   Each map is read once; no alignment of the base pointers, of H * W or of W is assumed.  Per row i:
+ *     counts [N][2] int32  = |est and gt|, |est or gt|
+ *     boxes  [N][2][4] int32 = the inclusive bounds x1, y1, x2, y2 of est, then of gt;  an EMPTY silhouette is (0, 0, -1, -1), as
+ *                     gdrn_scene_gt_visibility writes it
+ *     err    [N][2] fp64, contraction off:
+ *       err[i][0] = union > 0 ? 1.0 - (double)inter / (double)union : 1.0                     (cus / cou_mask, pose_error.py:479-484, :526-531)
+ *       err[i][1] = 1.0 - iou(xywh(est box), xywh(gt box)),  xywh = x1, y1, x2 - x1 + 1, y2 - y1 + 1   (cou_bb_proj as it is meant:
+ *                   misc.calc_2d_bbox_xywh(clip=False) + misc.iou);  1.0 if either silhouette is empty
+ *     iou(a, b) is misc.iou (lib/pysixd/misc.py:809-836) operation for operation in fp64: corners x + w, y + h; w_inter = min of the right corners -
+ *       max of the left ones, h_inter likewise; the intersection counts only when w_inter > 0 and h_inter > 0; then
+ *       (w_inter h_inter) / ((w_a h_a + w_b h_b) - w_inter h_inter), otherwise 0.  A NaN in either box gives 0.
+ *   workspace: gdrn_cou_maps_workspace_bytes(N) bytes of device memory (ten int32 per row), 4-byte aligned, no initialisation needed.
+ * gdrn_cou_bb: err [N] fp64 = 1.0 - iou(bb_est[i], bb_gt[i]) of N pairs of fp64 x, y, w, h boxes [N][4] (pose_error.cou_bb), one thread per pair.
+ * Status: GDRN_ERR_ARG for an unknown kind, N < 0, H or W < 1, H * W of 2^31 - 2048 and more, or (N > 0) a NULL pointer;  GDRN_ERR_SHAPE for
+ *   N * ceil(H W / 2048) beyond an int.  Everything is checked on the host before a stream or a device pointer is touched.  N == 0 launches
+ *   nothing and succeeds.  gdrn_cou_maps_workspace_bytes: GDRN_ERR_ARG for N < 0.  No call allocates or reads anything back. */
+enum { GDRN_COU_DEPTH = 0, GDRN_COU_MASK = 1 };
+long long gdrn_cou_maps_workspace_bytes(int N);
+int gdrn_cou_maps(const void* est, const void* gt, int kind, int N, int H, int W, double* err, int* counts, int* boxes, void* workspace,
+                  void* stream);
+int gdrn_cou_bb(const double* bb_est, const double* bb_gt, int N, double* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
