@@ -816,6 +816,100 @@ def make_cou_inputs(case, seed=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# estimates and depth frames of the depth refinement (gdrnet_amd.refine)
+# ----------------------------------------------------------------------------------------------
+REFINE_SEEDS = {"sphere": 231, "mixed": 232, "noisy": 233, "degenerate": 234}
+REFINE_CASES = tuple(REFINE_SEEDS)
+REFINE_OCCLUDER = 0.05   # metres in front of the object's nearest point
+
+
+def _refine_starts(seed, R_gt, t_gt, target, deg, mm):
+    """the ground truth `target[k]` turned by deg[k] degrees about a hashed axis through the model origin and moved by mm[k] millimetres along a
+    hashed direction"""
+    n = len(target)
+    axis, direction = hash_normal(seed, "start/axis", (n, 3)), hash_normal(seed, "start/dir", (n, 3))
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    direction /= np.linalg.norm(direction, axis=1, keepdims=True)
+    R0 = _axis_angle(axis, np.asarray(deg, dtype=np.float64)) @ R_gt[target]
+    t0 = t_gt[target] + 1e-3 * np.asarray(mm, dtype=np.float64)[:, None] * direction
+    return R0, t0
+
+
+def make_refine_inputs(case, seed=None):
+    """Inputs of the depth refinement (gdrnet_amd.refine), fp64, metres, built from make_render_inputs' meshes and ground-truth poses.  The depth
+    frames are not in here: ``refine_scene(inp, depth_gt)`` composes them from renders of the ground truth (the device's or the host's).
+
+    "sphere"      the 96 x 128 scene of make_render_inputs("sphere"); two estimates of its one pose: 5 degrees / 5 mm and 2 degrees / 2 mm off
+    "mixed"       the 120 x 160 scene of make_render_inputs("mixed") (icosphere, cube, rectangle, rectangle, cube); ground truths {0, 1, 2} in frame
+                  0, {3, 4} in frame 1; one estimate per ground truth, 5 / 5 off (even rows) or 2 / 2 off (odd rows), and a second estimate of the
+                  icosphere, 2 / 2 off (row 5).  ``convergent`` = the rows of the icosphere: a cube seen on two faces slides along their common
+                  edge under point-to-plane ICP, and a rectangle leaves three directions unobservable
+    "noisy"       a LIST of two inputs: "sphere", and the icosphere of "mixed" alone in its frame, each with the frame rounded to whole
+                  millimetres (a BOP depth PNG) behind an occluder REFINE_OCCLUDER in front of the left third of the object's box
+    "degenerate"  the fronto-parallel rectangle of make_render_inputs("watertight"), which fills its 64 x 64 frame up to the last row and column:
+                  all normals are equal.  Row 0: 0.2 degrees / 2 mm off (within the distance gate everywhere); row 1: moved out of the frame; row 2: behind the camera
+
+    Keys: vertices, faces (per class), gt_labels, R_gt, t_gt, gt_frame [G]; labels, target (its ground truth), R0, t0, K, frame, start_deg,
+    start_mm [N]; num_frames, H, W, near, far, round_mm, occluded (ground truths behind an occluder), convergent (rows), seed."""
+    if case not in REFINE_SEEDS:
+        raise ValueError(case)
+    seed = REFINE_SEEDS[case] if seed is None else seed
+    if case == "noisy":
+        parts = []
+        for k, base in enumerate(("sphere", "mixed")):
+            inp = make_refine_inputs(base, seed + 1000 * k)
+            keep = [i for i, g in enumerate(inp["target"]) if g == 0]   # the icosphere's rows
+            for key in ("labels", "target", "R0", "t0", "K", "frame", "start_deg", "start_mm"):
+                inp[key] = inp[key][keep]
+            for key in ("gt_labels", "R_gt", "t_gt", "gt_frame"):
+                inp[key] = inp[key][:1]
+            inp.update(num_frames=1, round_mm=True, occluded=(0,), convergent=tuple(range(len(keep))), case="noisy/" + base)
+            parts.append(inp)
+        return parts
+    base = make_render_inputs({"sphere": "sphere", "mixed": "mixed", "degenerate": "watertight"}[case])
+    R_gt, t_gt, gt_labels = base["R"], base["t"], np.asarray(base["labels"], dtype=np.int64)
+    if case == "sphere":
+        target, deg, mm, gt_frame = [0, 0], [5.0, 2.0], [5.0, 2.0], [0]
+        convergent = (0, 1)
+    elif case == "mixed":
+        target, deg, mm, gt_frame = [0, 1, 2, 3, 4, 0], [5.0, 2.0, 5.0, 2.0, 5.0, 2.0], [5.0, 2.0, 5.0, 2.0, 5.0, 2.0], [0, 0, 0, 1, 1]
+        convergent = (0, 5)
+    else:
+        target, deg, mm, gt_frame = [0, 0, 0], [0.2, 0.0, 0.0], [2.0, 0.0, 0.0], [0]
+        convergent = ()
+    target, gt_frame = np.array(target, dtype=np.int64), np.array(gt_frame, dtype=np.int64)
+    R0, t0 = _refine_starts(seed, R_gt, t_gt, target, deg, mm)
+    if case == "degenerate":
+        t0[1] = t_gt[0] + np.array([50.0, 0.0, 0.0])
+        t0[2] = t_gt[0] * np.array([1.0, 1.0, -1.0])
+    return dict(vertices=base["vertices"], faces=base["faces"], gt_labels=gt_labels, R_gt=R_gt, t_gt=t_gt, gt_frame=gt_frame,
+                labels=gt_labels[target], target=target, R0=R0, t0=t0, K=base["K"][target], frame=gt_frame[target],
+                start_deg=np.array(deg), start_mm=np.array(mm), num_frames=int(gt_frame.max()) + 1, H=base["H"], W=base["W"], near=base["near"],
+                far=base["far"], round_mm=False, occluded=(), convergent=convergent, seed=seed, case=case)
+
+
+def refine_scene(inp, depth_gt):
+    """The observed frames [F,H,W] fp32 of a make_refine_inputs scene from the depth maps ``depth_gt`` [G,H,W] of its ground truths (the host
+    rasterizer's or the device's): per frame the nearest ground-truth surface, 0 (no measurement) where there is none; for a ground truth in
+    ``occluded`` a block REFINE_OCCLUDER in front of its nearest point over the left third of its bounding box; with ``round_mm`` every depth
+    rounded to whole millimetres; one rounding to fp32."""
+    depth_gt = np.asarray(depth_gt, dtype=np.float64)
+    G, H, W = depth_gt.shape
+    out = np.full((inp["num_frames"], H, W), np.inf)
+    for g in range(G):
+        f, d = int(inp["gt_frame"][g]), depth_gt[g]
+        out[f] = np.where((d > 0) & (d < out[f]), d, out[f])
+    out[np.isinf(out)] = 0.0
+    for g in inp["occluded"]:
+        ys, xs = np.nonzero(depth_gt[g] > 0)
+        x1, x2 = int(xs.min()), int(xs.max())
+        out[int(inp["gt_frame"][g]), int(ys.min()) : int(ys.max()) + 1, x1 : x1 + (x2 - x1 + 1) // 3] = depth_gt[g][depth_gt[g] > 0].min() - REFINE_OCCLUDER
+    if inp["round_mm"]:
+        out = np.round(out * 1000.0) / 1000.0
+    return out.astype(np.float32)
+
+
+# ----------------------------------------------------------------------------------------------
 # estimates of the YCB-V score tables (gdrnet_amd.sixd_scores, golden G18)
 # ----------------------------------------------------------------------------------------------
 SIXD_SCORE_SEEDS = {"sym": 191}

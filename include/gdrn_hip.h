@@ -1199,6 +1199,59 @@ int gdrn_cou_maps(const void* est, const void* gt, int kind, int N, int H, int W
                   void* stream);
 int gdrn_cou_bb(const double* bb_est, const double* bb_gt, int N, double* err, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Depth refinement of estimated poses on the device (added within ABI 5: new entry points, nothing changed): projective point-to-plane ICP of N
+ * estimates against observed depth frames, the usual last step of an RGB-D entry before scoring.  The reference is RGB-only and has no
+ * counterpart; like the PnP entry points these are pinned to geometry and to an fp64 host restatement (tests/icp_host.py).  All arithmetic is
+ * fp64, contraction off, on the fp32 depths as stored.  No floating-point atomics: every sum has a fixed order, the same call gives the same
+ * bits, and the instances of a batch do not influence each other.
+ *
+ *   depth_ren   [N][H][W] fp32: the model under the current pose (gdrn_render_depth's map), 0 = nothing drawn
+ *   depth_scene [F][H][W] fp32: the observed frames in metres, 0 = no measurement;  frame [N] int32 (device) / frame_host (the same values on
+ *               the host, range-checked against F before any launch): the frame of each estimate
+ *   K           [N][3][3] fp64, upper triangular, as for gdrn_render_depth
+ *
+ * rays    d(x, y) = K^-1 [x, y, 1] on integer pixel coordinates, the ray the rasterizer samples (dy = (y - cy) / fy, dx = ((x - sk dy) - cx) / fx,
+ *         third component 1);  p = depth_ren[i][y][x] d is the model surface, q = depth_scene[frame[i]][y][x] d the observation.
+ * normal  of the observation at (x, y), computed on the fly:  a = q(x+1, y) - q(x-1, y),  b = q(x, y+1) - q(x, y-1),  c = a x b,
+ *         n = c / |c|, |c| = sqrt((cx cx + cy cy) + cz cz).  Valid when the pixel is not on the frame's border, all five observed depths
+ *         are > 0, each neighbour's depth differs from the centre's by at most normal_gate, and |c| > 0.  The sign of n is immaterial.
+ * pair    pixel (x, y) of instance i is a pair when depth_ren > 0, the normal is valid and |depth_scene - depth_ren| <= dist_gate.  (NaN
+ *         depths fail every comparison.)
+ * system  r = n . (p - q), evaluated as (depth_ren - depth_scene) ((nx dx + ny dy) + nz): the difference of the two fp32 depths is exact in
+ *         fp64;  J = [p x n, n] (rotation first);  A = sum J J^T, b = sum J r, sq = sum r^2, pairs = the integer count.
+ *         sys [N][28] fp64 = the 21 entries of A's upper triangle row by row (A00 .. A05, A11 .. A15, .., A55), b (6), sq.
+ * step    an instance is DEGENERATE when pairs < min_pairs, when a diagonal entry of A is not > 0, or when a pivot of the Cholesky
+ *         factorisation of S A S, S = diag(A_ii^-1/2) -- the remainder of a diagonal entry before its square root -- is not >= 1e-9.  It keeps
+ *         the pose it had and is frozen.  Otherwise xi = (w, v) solves A xi = -b (through that factorisation) and
+ *         R <- exp([w]x) R,  t <- exp([w]x) t + v,  exp by Rodrigues (sin(th) / th and 2 sin^2(th / 2) / th^2), I + [w]x below |w| = 1e-12.
+ *         A step with |w| < 1e-10 and |v| < 1e-10 |t| (t before the step) is applied and freezes the instance as CONVERGED.
+ *
+ * gdrn_icp_accumulate: one accumulation on given renders: sys [N][28] fp64 and pairs [N] int32.  One workgroup per (instance, band of 16
+ *   rows) writes its slab into `workspace`; a second launch combines the bands in ascending order.
+ * gdrn_icp_step: one solve and update from combined systems.  R [N][3][3], t [N][3] fp64 in/out;  state [N][2] int32 in/out = the status
+ *   (GDRN_ICP_RUNNING to start with) and the number of steps applied so far;  an instance that is not RUNNING is left alone.
+ * gdrn_icp_refine: the mesh table, labels, near and far exactly as gdrn_render_depth takes them;  R, t in/out.  `iters` times on the one stream:
+ *   gdrn_render_depth into depth_ren_scratch [N][H][W] fp32, the accumulate pass, the step -- which combines the slabs in its prologue, with the
+ *   operation sequence of gdrn_icp_accumulate's second launch: the same bits.  Nothing is read back.  Outputs, per instance:
+ *     ok [N] int32 = 0 iff it was found degenerate;  iters_done [N] int32 = the steps applied;  pairs [N] int32 and rms [N] fp64 =
+ *     sqrt(sq / pairs) of the last system accumulated while it was running, i.e. the residual before its last step (NaN when pairs == 0;
+ *     iters == 0: ok 1, pairs 0, rms NaN, the pose untouched).
+ *   workspace (both calls): gdrn_icp_workspace_bytes(N, H, W) bytes of device memory, 8-byte aligned, no initialisation needed.
+ * Status: GDRN_ERR_ARG for N < 0, H or W < 1, H * W of 2^31 - 1024 and more, gates that are not > 0, iters < 0, min_pairs < 6, a label or a frame
+ *   out of range, the rasterizer's argument rules, or (N > 0) a NULL pointer or a misaligned workspace;  GDRN_ERR_SHAPE for N > 65535 and the
+ *   rasterizer's shape rules.  Everything is checked on the host before a stream or a device pointer is touched;  N == 0 launches nothing. */
+enum { GDRN_ICP_RUNNING = 0, GDRN_ICP_CONVERGED = 1, GDRN_ICP_DEGENERATE = 2 };
+long long gdrn_icp_workspace_bytes(int N, int H, int W);
+int gdrn_icp_accumulate(const float* depth_ren, const float* depth_scene, const int* frame, const int* frame_host, int F, const double* K, int N,
+                        int H, int W, double dist_gate, double normal_gate, double* sys, int* pairs, void* workspace, void* stream);
+int gdrn_icp_step(const double* sys, const int* pairs, int N, int min_pairs, double* R, double* t, int* state, void* stream);
+int gdrn_icp_refine(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off, const int* nfaces, int C,
+                    int f_max, const int* labels, const int* labels_host, double* R, double* t, const double* K, int N, const float* depth_scene,
+                    const int* frame, const int* frame_host, int F, int H, int W, double near, double far, int iters, double dist_gate,
+                    double normal_gate, int min_pairs, float* depth_ren_scratch, int* ok, int* iters_done, int* pairs, double* rms,
+                    void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
