@@ -17,12 +17,11 @@
 // The accumulation order (tap 0..8, k-step 0 then 1) and the epilogue arithmetic (acc + bias (+ identity), ReLU, one rounding to the storage
 // format) are the two-launch path's: the result is BIT-IDENTICAL to conv1 -> conv2 on the halo kernel (tests/test_kernels_gpu.py).
 #include <algorithm>
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
 #include "common.h"
-#include "../../include/gdrn_hip.h"
+#include "launch_host.h"
 
 namespace {
 
@@ -207,12 +206,7 @@ extern "C" int gdrn_block64_eval(const void* x, const void* w1, const float* b1,
     if (dtype != GDRN_DT_H16) return GDRN_ERR_ARG;
     if (!gdrn_block64_eval_ok(N, H, W, dtype)) return GDRN_ERR_SHAPE;
     constexpr size_t smem = XBYTES + ABYTES;
-    static std::once_flag once;
-    static bool attr_ok = false;
-    std::call_once(once, [] {
-        attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&block64_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess;
-    });
-    if (!attr_ok) return GDRN_ERR_LAUNCH;
+    if (!lds_limit_once<&block64_eval_kernel>(smem)) return GDRN_ERR_LAUNCH;
     const int grid = N * (H / TH) * (W / TW);
     GDRN_LAUNCH(block64_eval_kernel, dim3(grid), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), (const bf16_t*)x, (const bf16_t*)w1, b1,
                 (const bf16_t*)w2, b2, (bf16_t*)y, N, H, W);

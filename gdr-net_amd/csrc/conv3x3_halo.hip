@@ -21,11 +21,10 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
 
 #include "common.h"
 #include "halo_xf.h"
-#include "../../include/gdrn_hip.h"
+#include "launch_host.h"
 
 namespace {
 
@@ -71,30 +70,6 @@ __global__ __launch_bounds__(256) void pack_wfrag_kernel(const T* __restrict__ s
     }
 }
 
-#ifdef HALO_DBG
-__device__ unsigned long long* g_halo_dbg;
-__device__ __forceinline__ unsigned long long halo_clock() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-struct HaloDbg {
-    unsigned long long t[6] = {0, 0, 0, 0, 0, 0};
-    int slot, lane;
-    __device__ ~HaloDbg() {
-        t[4] = halo_clock();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        t[5] = halo_clock();
-        if (lane == 0 && g_halo_dbg)
-            for (int i = 0; i < 6; ++i) g_halo_dbg[(size_t)slot * 8 + i] = t[i];
-    }
-};
-extern "C" int gdrn_halo_set_dbg(unsigned long long* buf) { return hipMemcpyToSymbol(HIP_SYMBOL(g_halo_dbg), &buf, sizeof(buf)) == hipSuccess ? 0 : -3; }
-#define HALO_STAMP(i_) hdbg_.t[i_] = halo_clock();
-#else
-#define HALO_STAMP(i_)
-#endif
-
 // KS = 2 (round 5): the EIGHT-wave form of the same tile for grids that give a CU one workgroup (8x8 - 16x16 maps at bs = 64: 256 workgroups =
 // one wave per SIMD, every LDS / L2 / MFMA latency exposed).  Waves 4-7 are a second copy of waves 0-3 -- same pixels, same channels, same
 // LDS patch -- that takes k-step 1 of every tap stage while the first copy takes k-step 0: each wave walks HALF the reduction (one 1 KiB
@@ -122,12 +97,6 @@ __global__ __launch_bounds__(256 * KS, KS == 2 ? 1 : ((BN == 64 && TW == 16 && s
     const int grp = KS == 2 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) : 0;   // wave group = k-step of every tap stage
     const int tid = threadIdx.x & 255, wave = tid >> 6;    // tid: thread index inside the wave group
     const int g = lane >> 4, r16 = lane & 15;
-#ifdef HALO_DBG
-    HaloDbg hdbg_;
-    hdbg_.slot = (int)blockIdx.x * 4 + wave;
-    hdbg_.lane = lane;
-#endif
-    HALO_STAMP(0)
     // the data-gradient chain shares its CUs with a side-stream weight-gradient launch (engine: wgrad_stream): its waves go first
     __builtin_amdgcn_s_setprio(2);
 
@@ -280,9 +249,7 @@ __global__ __launch_bounds__(256 * KS, KS == 2 ? 1 : ((BN == 64 && TW == 16 && s
         WRITEP(q0, u0, 0, 0, 0) WRITEP(q1, u1, 0, 1, 0) WRITEP(q2, u2, 0, 2, 0) WRITEP(q3, u3, 0, 3, 0) WRITEP(q4, u4, 0, 4, 0)
         WRITEP(q5, u5, 0, 5, 0) WRITEP(q6, u6, 0, 6, 0) WRITEP(q7, u7, 0, 7, 0) WRITEP(q8, u8, 0, 8, 0)
     }
-    HALO_STAMP(1)
     __syncthreads();
-    HALO_STAMP(2)
 
     // One tap stage = 2 k-steps x (FN weight frags in registers) x (FM pixel frags from LDS at immediate offsets), software
     // pipelined over the k-steps: the LDS reads of k-step 1 are issued before the MFMAs of k-step 0, and the reads of the
@@ -355,7 +322,6 @@ __global__ __launch_bounds__(256 * KS, KS == 2 ? 1 : ((BN == 64 && TW == 16 && s
         if (more_p) { WRITEP(rp1, rq1, pb ^ 1, 7, kc + 1) WRITEP(rp2, rq2, pb ^ 1, 8, kc + 1) }
         __syncthreads();
     }
-    HALO_STAMP(3)
 #undef LOADW
 #undef LOADP
 #undef WRITEP
@@ -650,20 +616,12 @@ __global__ __launch_bounds__(256 * KS, KS == 2 ? 1 : ((BN == 64 && TW == 16 && s
     }
 }
 
-constexpr int XF_MAX_CIN = 512;  // channels of the operand-transform table
-
 template <typename T, int TH, int TW, int BN, int XF, int KS = 1>
 int launch(const gdrn_conv_params& p, int N, hipStream_t st) {
     constexpr size_t smem = 2 * 2 * (size_t)half_bytes((TH + 2) * (TW + 2));
     constexpr size_t xbytes = KS == 2 ? (size_t)4 * (BN / 64) * (TH * TW / 16) * 64 * 16 : 0;   // accumulator exchange of the 8-wave form
     constexpr size_t smem_max = std::max(smem + xf_nk(XF) * XF_MAX_CIN * sizeof(float), xbytes);
-    static std::once_flag attr_once;
-    static bool attr_ok = false;
-    std::call_once(attr_once, [] {
-        attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<T, TH, TW, BN, XF, KS>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max) == hipSuccess;
-    });
-    if (!attr_ok) return GDRN_ERR_LAUNCH;
+    if (!lds_limit_once<&conv3x3_halo_kernel<T, TH, TW, BN, XF, KS>>(smem_max)) return GDRN_ERR_LAUNCH;
     const int grid = N * (p.Ho / TH) * (p.Wo / TW) * cdiv(p.Cout, BN);
     // a single 128-byte channel chunk (Cin = 64) never touches the second patch buffer: half the LDS -> a third workgroup per
     // CU on the 64-channel variants (142 VGPRs), whose runs are all prologue / one chunk / epilogue
@@ -695,12 +653,7 @@ int launch_tile_f32(const gdrn_conv_params& p, int tw, int N, hipStream_t st) {
 
 }  // namespace
 
-// second-generation kernel (conv3x3_v3.hip), selected by p->w_frag == 2
-int gdrn_v3_config(const gdrn_conv_params* p);
-int gdrn_v3_preferred(const gdrn_conv_params* p);
-int gdrn_v3_tile(const gdrn_conv_params* p, int* th, int* tw, int* bn);
-int gdrn_v3_launch(const gdrn_conv_params* p, void* stream);
-
+// (the second-generation kernel, conv3x3_v3.hip, is selected by p->w_frag == 2: gdrn_v3_* in launch_host.h)
 // operand layout the library prefers for a shape: 2 = gdrn_pack_wfrag32 (v3 kernel), 1 = gdrn_pack_wfrag, 0 = no halo tiling
 // (p->w_frag carries the caller's policy INTO this query: 0 = the library's choice -- the second-generation kernel where it measured faster --,
 //  1 = never the second-generation kernel, 2 = wherever it covers the shape; A/B runs and the plan variants of the tests)
@@ -777,29 +730,19 @@ extern "C" int gdrn_conv3x3_halo(const gdrn_conv_params* pp, void* stream) {
     if (th == 0) return GDRN_ERR_SHAPE;
     if (p.Cin <= 0 || (p.Cin * esz) % ROWB != 0 || (p.x_cs * esz) % 16 != 0 || p.Cout <= 0 || (p.y_cs & 3)) return GDRN_ERR_SHAPE;
     if (bn == 128 && ((p.y_cs & 7) || (p.addend && (p.add_cs & 7)) || (p.bnb_x && (p.bnb_cs & 7)))) return GDRN_ERR_SHAPE;  // 16-byte epilogue accesses
-    const int hw = p.Ho * p.Wo;
-    if (p.M <= 0 || p.M % hw != 0) return GDRN_ERR_SHAPE;
+    const int N = halo_images(p);
+    if (N == 0) return GDRN_ERR_SHAPE;
     if (p.w_rows < cdiv(p.Cout, bn) * bn) return GDRN_ERR_SHAPE;
     if (p.addend && (p.add_cs & 3)) return GDRN_ERR_SHAPE;
     if (p.w_frag < 0 || p.w_frag > 2) return GDRN_ERR_ARG;   // (ABI 1's padding field: an uninitialised value must not pick a kernel)
     if (p.halo_waves != 0 && p.halo_waves != 4 && p.halo_waves != 8) return GDRN_ERR_ARG;
-    if (p.bnb_x) {  // fused BatchNorm-backward statistics: fast epilogue only
-        if (!p.bnb_mean || !p.bnb_invstd || !p.bnb_rows || (p.bnb_scale != nullptr) != (p.bnb_shift != nullptr)) return GDRN_ERR_ARG;
-        if (p.bias || p.act || p.out_f32 || (p.Cout % bn) || (p.bnb_cs & 3) || p.bnb_cs < p.Cout) return GDRN_ERR_SHAPE;
-        if ((unsigned long long)p.M * (unsigned long long)p.bnb_cs * 4ull >= (1ull << 32)) return GDRN_ERR_SHAPE;
-    }
-    if ((unsigned long long)p.M * (unsigned long long)std::max(p.y_cs, p.add_cs) * 4ull >= (1ull << 32)) return GDRN_ERR_SHAPE;  // 32-bit offsets
+    if (const int e = halo_bnb_rules(p, bn, 4)) return e;
+    if (!fits_u32(p.M, std::max(p.y_cs, p.add_cs), 4)) return GDRN_ERR_SHAPE;  // 32-bit offsets
     // ... and so are the patch offsets of the kernel (poff = pixel * x_cs * sizeof(T) + chunk; xf_x2 and xf_out are indexed with them too): with
-    // x_cs > y_cs (fp32), or x_cs > 2 * max(y_cs, add_cs) (16-bit), the line above does not cover them (gdrn_v3_launch has the same check)
-    if ((unsigned long long)p.M * (unsigned long long)p.x_cs * (unsigned long long)esz >= (1ull << 32)) return GDRN_ERR_SHAPE;
+    // x_cs > y_cs (fp32), or x_cs > 2 * max(y_cs, add_cs) (16-bit), the line above does not cover them
+    if (!fits_u32(p.M, p.x_cs, esz)) return GDRN_ERR_SHAPE;
     if (p.dtype == GDRN_DT_F32 && (p.xf_mode || p.bnb_x)) return GDRN_ERR_ARG;   // transforms / fused BatchNorm-backward epilogue: 16-bit only
-    if (p.xf_mode) {  // operand transform while staging
-        if (p.xf_mode < 0 || p.xf_mode > 4 || !p.xf_c || p.Cin > XF_MAX_CIN || (p.Cin & 7)) return GDRN_ERR_ARG;
-        if (p.xf_mode >= 2 && !p.xf_x2) return GDRN_ERR_ARG;
-        if (p.xf_mode == 4 && (!p.xf_msc || !p.xf_msh)) return GDRN_ERR_ARG;
-        if (p.xf_mode != 2 && p.xf_c2) return GDRN_ERR_ARG;
-    }
-    const int N = p.M / hw;
+    if (const int e = halo_xf_rules(p)) return e;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (p.dtype == GDRN_DT_F32) return launch_tile_f32(p, tw, N, st);
     switch (p.xf_mode) {

@@ -26,7 +26,7 @@
 
 #include "common.h"
 #include "halo_xf.h"
-#include "../../include/gdrn_hip.h"
+#include "launch_host.h"
 
 namespace {
 
@@ -50,34 +50,8 @@ __device__ __forceinline__ void dma16(const void* gbase, unsigned voff, unsigned
                  : "memory");
 }
 
-#ifdef V3_DBG
-// bring-up instrumentation (tools/v3dbg.py builds this file alone with -DV3_DBG): cycle stamps per wave
-__device__ unsigned long long* g_v3_dbg;
-__device__ __forceinline__ unsigned long long v3_clock() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-struct V3Dbg { unsigned long long wait_mem = 0, wait_bar = 0; };
-#define V3_DBG_ARG , V3Dbg& dbg_
-#define V3_DBG_PASS , dbg_
-#else
-#define V3_DBG_ARG
-#define V3_DBG_PASS
-#endif
-
 template <int N>
-__device__ __forceinline__ void wait_barrier(int dummy_ V3_DBG_ARG) {
-#ifdef V3_DBG
-    const unsigned long long ta = v3_clock();
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-    const unsigned long long tb = v3_clock();
-    asm volatile("s_barrier" ::: "memory");
-    const unsigned long long tc = v3_clock();
-    dbg_.wait_mem += tb - ta;
-    dbg_.wait_bar += tc - tb;
-    return;
-#endif
+__device__ __forceinline__ void wait_barrier() {
     // own DMAs (all but the last N loads) landed, own LDS traffic drained, then the workgroup barrier: everybody's DMA of the next unit
     // is visible and everybody has finished reading the previous unit's slot.  One asm statement with a memory clobber: neither
     // hipcc's LDS reads nor the DMA statements move across it.
@@ -160,24 +134,6 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv3x3_v3_kernel(const gdrn_
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef V3_DBG
-    const unsigned long long t_entry = v3_clock();
-    struct DbgOut {
-        unsigned long long te, *tp, *t0, *t1; V3Dbg* d; int slot, lane;
-        unsigned long long e1 = 0, e2 = 0;
-        __device__ ~DbgOut() {
-            const unsigned long long tend = v3_clock();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const unsigned long long tdrain = v3_clock();
-            if (lane == 0 && g_v3_dbg) {
-                unsigned long long* o = g_v3_dbg + (size_t)slot * 12;
-                o[0] = te; o[1] = *tp; o[2] = *t0; o[3] = *t1; o[4] = tend; o[5] = d->wait_mem; o[6] = d->wait_bar;
-                unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); o[7] = xcc;
-                o[8] = e1; o[9] = e2; o[10] = tdrain;
-            }
-        }
-    };
-#endif
     const int wn = wave % WN, wm = (wave / WN) % WM, wk = wave / (WN * WM);
     const int l5 = lane & 31, hh = lane >> 5;
 
@@ -200,16 +156,8 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv3x3_v3_kernel(const gdrn_
     const int total_units = kch * UPC;
 
     // ---- weight stream: unit g = kc*UPC + U is KSU*NFRT blocks of 1 KiB at w + g*wstride; this wave moves DPW consecutive blocks
-#ifndef V3_VAR
-#define V3_VAR 0
-#endif
-    constexpr bool HALF_DMA = (V3_VAR & 1) && K::NW == 8;   // experiment: only waves 0..3 feed the ring
-    constexpr int DPWX = HALF_DMA ? 2 * K::DPW : K::DPW;
     const int NFRT = p.w_rows >> 5;
-    const int j0 = (HALF_DMA ? (wave & 3) : wave) * DPWX;  // first block of this wave inside a unit: (k-substep j0 / NFRB, fragment j0 % NFRB)
-    if constexpr ((V3_VAR & 2) != 0) {
-        if (wave >= K::NW / 2) __builtin_amdgcn_s_setprio(1);
-    }
+    const int j0 = wave * K::DPW;  // first block of this wave inside a unit: (k-substep j0 / NFRB, fragment j0 % NFRB)
     const unsigned wlane = (unsigned)((((j0 / NFRB) * NFRT + nt * NFRB + (j0 % NFRB)) << 10) + lane * 16);
     const size_t wstride = (size_t)K::KSU * NFRT * 1024;
     const char* wg = reinterpret_cast<const char*>(p.w);
@@ -217,10 +165,8 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv3x3_v3_kernel(const gdrn_
     auto dma_w = [&](int g, int slot) {
         const int gc = g < total_units ? g : total_units - 1;  // past the end: a harmless reload into a free slot keeps the counts static
         const char* src = wg + (size_t)gc * wstride;
-        if (HALF_DMA && wave >= 4) return;
-        if ((V3_VAR & 8) && g > 2) return;   // knock-out experiment (wrong results): the ring is never refilled
 #pragma unroll
-        for (int i = 0; i < DPWX; ++i) dma16(src + i * 1024, wlane, ring_a + (unsigned)(slot * V3_UNIT + i * 1024));
+        for (int i = 0; i < K::DPW; ++i) dma16(src + i * 1024, wlane, ring_a + (unsigned)(slot * V3_UNIT + i * 1024));
     };
     dma_w(0, 0);
     dma_w(1, 1);
@@ -345,17 +291,8 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv3x3_v3_kernel(const gdrn_
                                                                       __builtin_bit_cast(bf16x8_t, fb_[b_]), acc[a_][b_]); \
     }
 
-#ifdef V3_DBG
-    V3Dbg dbg_;
-    const unsigned long long t_pro = v3_clock();
-#endif
     // first barrier: patch 0 complete, units 0 and 1 landed
-    wait_barrier<0>(0 V3_DBG_PASS);
-#ifdef V3_DBG
-    unsigned long long t_loop0 = v3_clock(), t_loop1 = 0, t_pro_ = t_pro;
-    dbg_.wait_mem = dbg_.wait_bar = 0;
-    DbgOut dbg_out_{t_entry, &t_pro_, &t_loop0, &t_loop1, &dbg_, (int)blockIdx.x * K::NW + wave, lane};
-#endif
+    wait_barrier<0>();
     dma_w(2, 2);
     {
         const unsigned char* pc0 = smem + K::OFF_P0 + lbase;
@@ -373,18 +310,14 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv3x3_v3_kernel(const gdrn_
             constexpr int U = decltype(Uc)::value;
             if constexpr (U > 0) {
                 // [A][B] weights of unit U+1 (issued one unit ago) landed everywhere; slot (U-1)%3 is free
-                wait_barrier<K::pd(U - 1)>(0 V3_DBG_PASS);
+                wait_barrier<K::pd(U - 1)>();
                 // [C] refill it with unit U+2
                 dma_w(gbase + U + 2, (U + 2) % V3_RING);
             }
             // [D] next chunk's patch: transform a landed slice, send the next DMA (always issued: static load counts)
-            if constexpr ((V3_VAR & 4) != 0) {   // knock-out experiment (wrong results): no patch traffic inside the loop
-            } else
             if constexpr (K::xf_slice(U) >= 0 && K::xf_slice(U) < NSL) {
                 if (more_p) xf_p(kc + 1, K::xf_slice(U), K::OFF_RAW + K::raw_slot(K::xf_slice(U)) * NIN * K::SLICE_BYTES, pb ^ 1);
             }
-            if constexpr ((V3_VAR & 4) != 0) {
-            } else
             if constexpr (K::dma_slice(U) >= 0 && K::dma_slice(U) < NSL) {
                 if constexpr (K::xf_slice(U) >= 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the raw slot's reads are done
                 dma_p(kc + 1, K::dma_slice(U), K::OFF_RAW + K::raw_slot(K::dma_slice(U)) * NIN * K::SLICE_BYTES);
@@ -413,16 +346,13 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv3x3_v3_kernel(const gdrn_
         static_for<UPC>(unit);
         // chunk boundary = the barrier of the next chunk's unit 0
         if (more_p) {
-            wait_barrier<K::pd(UPC - 1)>(0 V3_DBG_PASS);
+            wait_barrier<K::pd(UPC - 1)>();
             dma_w(gbase + UPC + 2, 2);   // (UPC + 2) % 3 == 2
         }
     }
 #undef V3_LDA
 #undef V3_LDB
 #undef V3_MM
-#ifdef V3_DBG
-    t_loop1 = v3_clock();
-#endif
     // every DMA (incl. the reloads past the end) landed and every wave is done with the LDS operands: LDS is scratch from here
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
@@ -623,13 +553,7 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv3x3_v3_kernel(const gdrn_
             }
             red_put(cwl + (a >> 1) * 64 + (a & 1) * 16, wsum, 16);
         }
-#ifdef V3_DBG
-        dbg_out_.e1 = v3_clock();
-#endif
         put_rows(p.stats);
-#ifdef V3_DBG
-        dbg_out_.e2 = v3_clock();
-#endif
     }
     const bool relu = p.act == 1;
     const char* ab2 = LEAN ? nullptr : ab;
@@ -672,13 +596,7 @@ int launch_v3(const gdrn_conv_params& p, int N, hipStream_t st) {
     using K = V3<TH, BN, WM, WN, WK, XF>;
     const size_t smem = K::smem_bytes(p.Cin);
     if (smem > 160 * 1024) return GDRN_ERR_SHAPE;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_v3_kernel<TH, BN, WM, WN, WK, XF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess)
-            return GDRN_ERR_LAUNCH;
-        attr_set = true;
-    }
+    if (!lds_limit_once<&conv3x3_v3_kernel<TH, BN, WM, WN, WK, XF>>(160 * 1024)) return GDRN_ERR_LAUNCH;
     const int grid = N * (p.Ho / TH) * (p.Wo / 16) * (p.Cout / BN);
     GDRN_LAUNCH((conv3x3_v3_kernel<TH, BN, WM, WN, WK, XF>), dim3(grid), dim3(K::NT), smem, st, p);
     GDRN_CHECK_LAUNCH();
@@ -743,10 +661,6 @@ extern "C" int gdrn_pack_wfrag32(const void* src, void* dst, int rows, int Cin, 
     return GDRN_OK;
 }
 
-#ifdef V3_DBG
-extern "C" int gdrn_v3_set_dbg(unsigned long long* buf) { return hipMemcpyToSymbol(HIP_SYMBOL(g_v3_dbg), &buf, sizeof(buf)) == hipSuccess ? 0 : -3; }
-extern "C" int gdrn_v3_launch_c(const gdrn_conv_params* pp, void* stream);
-#endif
 int gdrn_v3_launch(const gdrn_conv_params* pp, void* stream) {
     const gdrn_conv_params& p = *pp;
     const int cfg = gdrn_v3_config(pp);
@@ -754,22 +668,13 @@ int gdrn_v3_launch(const gdrn_conv_params* pp, void* stream) {
     const int bn = cfg == 1 ? 256 : 128;
     if ((p.x_cs & 7) || (p.y_cs & 7) || (p.addend && (p.add_cs & 7)) || (p.bnb_x && (p.bnb_cs & 7))) return GDRN_ERR_SHAPE;  // 16-byte accesses
     if (p.w_rows < p.Cout || (p.w_rows & 63) || (p.Cout % bn)) return GDRN_ERR_SHAPE;
-    const int hw = p.Ho * p.Wo;
-    if (p.M <= 0 || p.M % hw != 0) return GDRN_ERR_SHAPE;
-    if (p.bnb_x) {
-        if (!p.bnb_mean || !p.bnb_invstd || !p.bnb_rows || (p.bnb_scale != nullptr) != (p.bnb_shift != nullptr)) return GDRN_ERR_ARG;
-        if (p.bias || p.act || p.bnb_cs < p.Cout) return GDRN_ERR_SHAPE;
-        if ((unsigned long long)p.M * (unsigned long long)p.bnb_cs * 2ull >= (1ull << 32)) return GDRN_ERR_SHAPE;
-    }
-    if ((unsigned long long)p.M * (unsigned long long)(p.y_cs > p.add_cs ? p.y_cs : p.add_cs) * 2ull >= (1ull << 32)) return GDRN_ERR_SHAPE;  // 32-bit offsets
-    if ((unsigned long long)p.M * (unsigned long long)p.x_cs * 2ull >= (1ull << 32)) return GDRN_ERR_SHAPE;
-    if (p.xf_mode) {
-        if (p.xf_mode < 0 || p.xf_mode > 4 || !p.xf_c || p.Cin > 512) return GDRN_ERR_ARG;
-        if (p.xf_mode >= 2 && !p.xf_x2) return GDRN_ERR_ARG;
-        if (p.xf_mode == 4 && (!p.xf_msc || !p.xf_msh)) return GDRN_ERR_ARG;
-        if (p.xf_mode != 2 && p.xf_c2) return GDRN_ERR_ARG;
-    }
-    const int N = p.M / hw;
+    const int N = halo_images(p);
+    if (N == 0) return GDRN_ERR_SHAPE;
+    // (of the shared rules, gdrn_v3_config and the lines above have already refused out_f32, part channel tiles, bnb_cs & 3 and Cin & 7)
+    if (const int e = halo_bnb_rules(p, bn, 2)) return e;
+    if (!fits_u32(p.M, std::max(p.y_cs, p.add_cs), 2)) return GDRN_ERR_SHAPE;  // 32-bit offsets of the epilogue
+    if (!fits_u32(p.M, p.x_cs, 2)) return GDRN_ERR_SHAPE;   // ... and of the patch DMAs (poff; xf_x2 and xf_out are indexed with them too)
+    if (const int e = halo_xf_rules(p)) return e;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     switch (p.xf_mode) {
         case 0: return launch_v3_cfg<0>(p, cfg, N, st);
@@ -779,8 +684,3 @@ int gdrn_v3_launch(const gdrn_conv_params* pp, void* stream) {
         default: return launch_v3_cfg<4>(p, cfg, N, st);
     }
 }
-
-#ifdef V3_DBG
-extern "C" int gdrn_v3_launch_c(const gdrn_conv_params* pp, void* stream) { return gdrn_v3_launch(pp, stream); }
-extern "C" int gdrn_v3_tile_c(const gdrn_conv_params* p, int* th, int* tw, int* bn) { return gdrn_v3_tile(p, th, tw, bn); }
-#endif

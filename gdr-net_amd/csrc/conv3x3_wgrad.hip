@@ -21,7 +21,7 @@
 #include <utility>
 
 #include "common.h"
-#include "../../include/gdrn_hip.h"
+#include "launch_host.h"
 
 namespace {
 
@@ -174,9 +174,6 @@ __device__ __forceinline__ void wgrad_tile(const gdrn_wgrad_params& p, int bid, 
     // in the second half of stage pi (right behind the LDS write of patch pi + 1, which frees the registers) and are written in the middle of stage
     // pi + 1: ~17 MFMA groups (~1200 cycles) between a load and its use.  (Until r6: loads of patch pi + 1 in the first half of stage pi, written
     // behind its last group -- 9 to 18 groups; the probe build that re-fetches one cached patch showed a fifth of the kernel waiting there.)
-#ifdef WGRAD_PROBE_SAMEPATCH   // probe build (tools/wgrad_lat_probe.py): every stage re-fetches the first patch -- cache hits, the arithmetic of a stage unchanged
-#define ADVANCE_PATCH() {}
-#else
 #define ADVANCE_PATCH()                                                                               \
     {                                                                                                 \
         if (++pn_x == tiles_x) {                                                                      \
@@ -184,7 +181,6 @@ __device__ __forceinline__ void wgrad_tile(const gdrn_wgrad_params& p, int bid, 
             if (++pn_y == tiles_y) { pn_y = 0; ++pn_n; }                                              \
         }                                                                                             \
     }
-#endif
     LDD() LDX(0, x0) LDX(1, x1) LDX(2, x2) LDX(3, x3)
     if constexpr (G_::NX == 5) LDX(4, x4)
     WRITE_PATCH(0)
@@ -380,8 +376,8 @@ extern "C" int gdrn_conv3x3_wgrad_ok(const gdrn_wgrad_params* p) {
     // M / (Ho Wo) images of x must each end below 2^32 bytes (M <= 0 or no multiple of Ho Wo: the launcher's own refusal)
     if (p->M > 0) {
         const unsigned long long nimg = ((unsigned long long)p->M + (unsigned long long)p->Ho * p->Wo - 1) / ((unsigned long long)p->Ho * p->Wo);
-        if ((unsigned long long)p->M * (unsigned long long)p->dy_cs * 2ull >= (1ull << 32)) return 0;
-        if (nimg * (unsigned long long)p->Hi * (unsigned long long)p->Wi * (unsigned long long)p->x_cs * 2ull >= (1ull << 32)) return 0;
+        if (!fits_u32(p->M, p->dy_cs, 2)) return 0;
+        if (!fits_u32(nimg, p->Hi, p->Wi, p->x_cs, 2)) return 0;
     }
     if (p->stride == 1) return p->Hi == p->Ho && p->Wi == p->Wo && (p->Ho % 8) == 0;
     if (p->stride == 2) return p->Hi == 2 * p->Ho && p->Wi == 2 * p->Wo && (p->Ho % 4) == 0;
@@ -419,12 +415,7 @@ extern "C" int gdrn_conv3x3_wgrad(const gdrn_wgrad_params* pp, void* stream) {
     const int splits = gdrn_conv3x3_wgrad_splits(pp);
     if (splits <= 0) return GDRN_ERR_SHAPE;
     constexpr size_t smem = 2 * (size_t)stage_bytes<4>();
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    });
-    if (attr_err != hipSuccess) return GDRN_ERR_LAUNCH;
+    if (!lds_limit_once<&conv3x3_wgrad_kernel>(smem)) return GDRN_ERR_LAUNCH;
     GDRN_LAUNCH(conv3x3_wgrad_kernel, dim3(tiles * splits), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), p, npatch,
                        splits);
     GDRN_CHECK_LAUNCH();

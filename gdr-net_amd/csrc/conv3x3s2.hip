@@ -13,12 +13,11 @@
 // eight more MFMAs per k-step into a second accumulator set, its row-major operand gathered from global memory (2 KiB per wave and chunk).
 // Epilogue = the halo kernel's fast path: per-tile BatchNorm statistics rows (train mode), or bias + ReLU (eval mode: folded BatchNorm).
 #include <algorithm>
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
 #include "common.h"
-#include "../../include/gdrn_hip.h"
+#include "launch_host.h"
 
 namespace {
 
@@ -299,7 +298,7 @@ extern "C" int gdrn_conv3x3s2_ok(const gdrn_s2_params* p) {
     if (p->Cin <= 0 || (p->Cin % 64) || p->Cout <= 0 || (p->Cout % BN) || p->w_rows < p->Cout || (p->x_cs & 7) || p->x_cs < p->Cin) return 0;
     if ((p->y_cs & 7) || p->y_cs < p->Cout || p->act < 0 || p->act > 1) return 0;
     if (p->wd && ((p->yd_cs & 7) || p->yd_cs < p->Cout || p->wd_rows < p->Cout)) return 0;
-    if ((unsigned long long)p->N * p->Hi * p->Wi * p->x_cs * 2ull >= (1ull << 32)) return 0;   // 32-bit byte offsets of the patch loads
+    if (!fits_u32(p->N, p->Hi, p->Wi, p->x_cs, 2)) return 0;   // 32-bit byte offsets of the patch loads
     if (p->bnb_x && (p->wd || p->stats || p->bias || p->act || (p->bnb_cs & 7) || p->bnb_cs < p->Cout)) return 0;   // BatchNorm-backward epilogue: a plain launch
     return 1;
 }
@@ -314,12 +313,7 @@ namespace {
 template <bool DS, int TW_, bool BNB = false>
 int launch_s2(const gdrn_s2_params& p, hipStream_t st) {
     constexpr size_t smem = Geo<TW_>::PBYTES;
-    static std::once_flag once;
-    static bool attr_ok = false;
-    std::call_once(once, [] {
-        attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3s2_kernel<DS, TW_, BNB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess;
-    });
-    if (!attr_ok) return GDRN_ERR_LAUNCH;
+    if (!lds_limit_once<&conv3x3s2_kernel<DS, TW_, BNB>>(smem)) return GDRN_ERR_LAUNCH;
     const int grid = (p.N / Geo<TW_>::NI) * (p.Ho / TH) * (p.Wo / TW_) * (p.Cout / BN);
     GDRN_LAUNCH((conv3x3s2_kernel<DS, TW_, BNB>), dim3(grid), dim3(256), smem, st, p);
     GDRN_CHECK_LAUNCH();

@@ -18,12 +18,11 @@
 // FWD: the same sum IS the forward pass of nn.ConvTranspose2d(k = 3, s = 2, p = 1, output_padding = 1) (cdpn_rot_head_region.py:96-101: dy = its
 // input, dx = its output, w = [out channels][9][in channels]); the FWD epilogue is a forward conv's -- BatchNorm statistics rows or bias + ReLU.
 #include <algorithm>
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
 #include "common.h"
-#include "../../include/gdrn_hip.h"
+#include "launch_host.h"
 
 namespace {
 
@@ -353,7 +352,7 @@ extern "C" int gdrn_conv3x3s2_dgrad_ok(const gdrn_s2d_params* p) {
     if (p->bnb_x && ((p->bnb_cs & 3) || p->bnb_cs < p->Cin)) return 0;
     if (p->act < 0 || p->act > 1) return 0;
     if ((p->stats || p->bias || p->act) && (p->dyd || p->bnb_x)) return 0;   // forward (ConvTranspose) epilogue: a plain launch
-    if ((unsigned long long)p->N * p->Ho * p->Wo * std::max(p->dy_cs, p->dyd_cs) * 2ull >= (1ull << 32)) return 0;
+    if (!fits_u32(p->N, p->Ho, p->Wo, std::max(p->dy_cs, p->dyd_cs), 2)) return 0;
     if ((unsigned long long)p->N * p->Hi * p->Wi >= (1ull << 31)) return 0;
     return 1;
 }

@@ -16,7 +16,7 @@
 // with 4 consecutive output channels of one pixel (8/16-byte stores, per-channel BN statistics by a
 // 16-lane butterfly).
 #include "common.h"
-#include "../../include/gdrn_hip.h"
+#include "launch_host.h"
 
 template <>
 __device__ __forceinline__ f32x4_t mma_step<float>(uint4 a, uint4 b, f32x4_t c) {
@@ -531,13 +531,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && BM == 64 && BN == 128) ? 3 
 template <typename T, int BM, int BN>
 int launch(const gdrn_conv_params& p, hipStream_t st) {
     constexpr size_t smem = 512 + 2 * (size_t)(BM + BN) * ROWB;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return GDRN_ERR_LAUNCH;
-        attr_set = true;
-    }
+    if (!lds_limit_once<&conv_gemm_kernel<T, BM, BN>>(smem)) return GDRN_ERR_LAUNCH;
     const int NT = cdiv(p.Cout, BN);
     const int MT = (p.mode == 1) ? 4 * cdiv(p.M, BM) : cdiv(p.M, BM);
     GDRN_LAUNCH((conv_gemm_kernel<T, BM, BN>), dim3(MT * NT), dim3(256), smem, st, p);
@@ -582,7 +576,7 @@ extern "C" int gdrn_conv_gemm(const gdrn_conv_params* pp, void* stream) {
         if (p.bias || p.act || p.out_f32 || p.stats || (p.Cout % bn) || (p.bnb_cs & 7) || (p.y_cs & 7) || (p.addend && (p.add_cs & 7)) || p.bnb_cs < p.Cout)
             return GDRN_ERR_SHAPE;  // (rows of whole 16-byte groups: the epilogue's accesses)
         const unsigned long long rows_out = (p.mode == 1) ? 4ull * (unsigned long long)p.M : (unsigned long long)p.M;
-        if (rows_out * (unsigned long long)std::max(std::max(p.y_cs, p.add_cs), p.bnb_cs) * 2ull >= (1ull << 32)) return GDRN_ERR_SHAPE;  // 32-bit offsets
+        if (!fits_u32(rows_out, std::max(std::max(p.y_cs, p.add_cs), p.bnb_cs), 2)) return GDRN_ERR_SHAPE;  // 32-bit offsets
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (p.dtype == GDRN_DT_H16) {

@@ -14,7 +14,7 @@
 #include <cstdlib>
 
 #include "common.h"
-#include "../../include/gdrn_hip.h"
+#include "launch_host.h"
 
 namespace {
 
@@ -212,13 +212,7 @@ int launch(const gdrn_wgrad_params& p, hipStream_t st) {
     constexpr int BKM = (ESZ == 2) ? 64 : 32;
     constexpr int PADB = (ESZ == 2) ? 32 : 64;
     constexpr size_t smem = 2 * (size_t)BKM * ((BCO * ESZ + PADB) + (BCI * ESZ + PADB));
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<T, BCO, BCI>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return GDRN_ERR_LAUNCH;
-        attr_set = true;
-    }
+    if (!lds_limit_once<&conv_wgrad_kernel<T, BCO, BCI>>(smem)) return GDRN_ERR_LAUNCH;
     const int tiles = cdiv(p.Cout, BCO) * (p.Cin / BCI) * p.KH * p.KW;
     int splits = p.splits;
     if (splits <= 0) {
