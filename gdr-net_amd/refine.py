@@ -4,10 +4,15 @@ The reference is RGB-only (``WITH_DEPTH=False``) and has no counterpart; this is
 pose (or ``pnp.poses_from_maps``) and the metric modules.  Per iteration the model is rendered under the current pose (``render.render_depth``'s
 launch), every pixel where the render and the observation lie within ``dist_gate`` of each other and the observation has a normal becomes a
 pair, and the 6 x 6 point-to-plane normal equations of every estimate are summed and solved; the pose is updated by left multiplication.  The
-association is by pixel: it refines estimates that already overlap the object.  There is no silhouette term (flat-faced objects keep their
-sliding directions) and there are no robust weights.  The arithmetic is stated with the entry points in ``include/gdrn_hip.h``; all of it is
-fp64, sums have a fixed order (the same call gives the same bits; the instances of a batch do not influence each other).  Nothing is read back
-inside ``icp_refine``.  There is no CPU fallback.
+association is by pixel: it refines estimates that already overlap the object within ``dist_gate`` -- an estimate further off along its viewing
+ray (the usual error of an RGB-only pose) goes through ``depth_align`` first, or through ``refine_rgbd``, which runs both.  There is no
+silhouette term (flat-faced objects keep their sliding directions) and there are no robust weights.  The arithmetic is stated with the entry
+points in ``include/gdrn_hip.h``; all of it is fp64, sums have a fixed order (the same call gives the same bits; the instances of a batch do
+not influence each other).  Nothing is read back inside ``icp_refine``.  There is no CPU fallback.
+
+``depth_align`` (csrc/depth_align.hip) is that coarse step: the estimate is shifted along its viewing ray by the exact median of observed
+minus rendered depth over the pixels where both exist and differ by at most ``gate``, a fixed number of times.  It corrects depth only: there
+is no lateral alignment, no mask gate, no silhouette term and no robust weighting beyond the median itself.
 """
 import torch
 
@@ -104,4 +109,95 @@ def icp_refine(meshes, labels, R0, t0, K, depth_scene, frame, iters=10, dist_gat
                                    meshes.num_classes, meshes.f_max, p(lab), lab_host.ctypes.data, p(R), p(t), p(K), N, p(scene), p(fr),
                                    fr_host.ctypes.data, F, H, W, float(near), float(far), iters, dist_gate, normal_gate, min_pairs, p(scratch),
                                    p(out["ok"]), p(out["iters_done"]), p(out["pairs"]), p(out["rms"]), p(ws), devargs.stream(dev)), "icp_refine")
+    return out
+
+
+def _align_args(gate, min_pairs, rounds=0):
+    gate, min_pairs, rounds = float(gate), int(min_pairs), int(rounds)
+    if not gate > 0.0:
+        raise ValueError(f"gate {gate} must be positive")
+    if min_pairs < 1 or rounds < 0:
+        raise ValueError(f"min_pairs {min_pairs} must be >= 1 and rounds {rounds} >= 0")
+    return gate, min_pairs, rounds
+
+
+def depth_offset(depth_ren, depth_scene, frame, gate=0.2, min_pairs=64):
+    """The median depth difference of N estimates on given renders: ``depth_ren`` [N,H,W] fp32 (e.g. ``render.render_depth``'s),
+    ``depth_scene`` [F,H,W] fp32 (metres, 0 = no measurement), ``frame`` [N].  A pixel is a pair where both depths are positive and
+    ``|depth_scene - depth_ren| <= gate``.  Returns a dict of device tensors: offset [N] fp64 (the exact median of ``depth_scene - depth_ren``
+    over the pairs; NaN with fewer than ``min_pairs`` pairs), pairs, covered (pixels the render covers) and ok [N] int32."""
+    gate, min_pairs, _ = _align_args(gate, min_pairs)
+    if not isinstance(depth_ren, torch.Tensor) or depth_ren.device.type != "cuda":
+        raise devargs.no_fallback("depth_ren", WHERE)
+    if depth_ren.dtype != torch.float32 or depth_ren.dim() != 3:
+        raise ValueError("depth_ren must be an fp32 [N, H, W] tensor")
+    scene = _scene(depth_scene)
+    ren = devargs.device_tensor(depth_ren, None, None, "depth_ren", WHERE)
+    if ren.shape[1:] != scene.shape[1:]:
+        raise ValueError(f"depth_ren {tuple(ren.shape)} and depth_scene {tuple(scene.shape)} differ in H, W")
+    if ren.device != scene.device:
+        raise ValueError(f"depth_ren is on {ren.device}, depth_scene on {scene.device}")
+    N, H, W = (int(s) for s in ren.shape)
+    dev = ren.device
+    F = int(scene.shape[0])
+    fr, fr_host = devargs.index_vector(frame, N, F, dev, "frame")
+    out = dict(offset=torch.empty(N, dtype=torch.float64, device=dev), pairs=torch.empty(N, dtype=torch.int32, device=dev),
+               covered=torch.empty(N, dtype=torch.int32, device=dev), ok=torch.empty(N, dtype=torch.int32, device=dev))
+    if N == 0:
+        return out
+    lib = cabi.load()
+    ws = devargs.workspace(lib.gdrn_depth_align_workspace_bytes(N, H, W), dev, "depth_align_workspace_bytes")
+    p = cabi.ptr
+    cabi.check(lib.gdrn_depth_offset(p(ren), p(scene), p(fr), fr_host.ctypes.data, F, N, H, W, gate, min_pairs, p(out["offset"]), p(out["pairs"]),
+                                     p(out["covered"]), p(out["ok"]), p(ws), devargs.stream(dev)), "depth_offset")
+    return out
+
+
+def depth_align(meshes, labels, R0, t0, K, depth_scene, frame, rounds=2, gate=0.2, min_pairs=64, near=render.NEAR, far=render.FAR):
+    """Coarse alignment of N estimates along their viewing rays, the step in front of ``icp_refine`` for estimates that are centimetres off
+    in depth (an RGB-only pose): ``rounds`` times (a fixed count) the model is rendered under the current pose, the median of
+    ``depth_scene - render`` over the pairs is taken (``depth_offset``) and the translation is scaled so that its depth grows by that offset
+    and the model origin keeps its image.  The arguments are those of ``icp_refine``; R0 is only read.  ``gate`` must exceed the depth error of
+    the estimates and stay below the distance to the background; it is a parameter, and its default of 0.2 m is not measured on real data.
+    Returns a dict of device tensors: t [N,3] fp64; ok [N] int32 (0: a round found fewer than ``min_pairs`` pairs -- the instance keeps the
+    translation it had and is left alone from then on); pairs, covered [N] int32 and offset [N] fp64 (NaN where ok is 0), those of the
+    instance's last evaluated round.  Nothing is read back.  The caller's tensors stay."""
+    gate, min_pairs, rounds = _align_args(gate, min_pairs, rounds)
+    R, t, K, N = devargs.poses(R0, t0, K, WHERE)
+    scene = _scene(depth_scene)
+    dev = R.device
+    if scene.device != dev:
+        raise ValueError(f"R0 is on {dev}, depth_scene on {scene.device}")
+    F, H, W = (int(s) for s in scene.shape)
+    lab, lab_host = devargs.index_vector(labels, N, meshes.num_classes, dev, "labels")
+    fr, fr_host = devargs.index_vector(frame, N, F, dev, "frame")
+    t = t.clone()   # in/out for the library; the caller's tensor stays
+    out = dict(t=t, ok=torch.empty(N, dtype=torch.int32, device=dev), pairs=torch.empty(N, dtype=torch.int32, device=dev),
+               covered=torch.empty(N, dtype=torch.int32, device=dev), offset=torch.empty(N, dtype=torch.float64, device=dev))
+    if N == 0:
+        return out
+    lib = cabi.load()
+    tb = meshes.on(dev)
+    scratch = torch.empty(N, H, W, dtype=torch.float32, device=dev)
+    ws = devargs.workspace(lib.gdrn_depth_align_workspace_bytes(N, H, W), dev, "depth_align_workspace_bytes")
+    p = cabi.ptr
+    cabi.check(lib.gdrn_depth_align(p(tb["verts"]), p(tb["faces"]), p(tb["vert_off"]), p(tb["nverts"]), p(tb["face_off"]), p(tb["nfaces"]),
+                                    meshes.num_classes, meshes.f_max, p(lab), lab_host.ctypes.data, p(R), p(t), p(K), N, p(scene), p(fr),
+                                    fr_host.ctypes.data, F, H, W, float(near), float(far), rounds, gate, min_pairs, p(scratch), p(out["ok"]),
+                                    p(out["pairs"]), p(out["covered"]), p(out["offset"]), p(ws), devargs.stream(dev)), "depth_align")
+    return out
+
+
+def refine_rgbd(meshes, labels, R0, t0, K, depth_scene, frame, rounds=2, gate=0.2, align_min_pairs=64, iters=10, dist_gate=0.02,
+                normal_gate=0.01, min_pairs=64, near=render.NEAR, far=render.FAR):
+    """``depth_align`` (``rounds``, ``gate``, ``align_min_pairs``), then ``icp_refine`` (``iters``, ``dist_gate``, ``normal_gate``,
+    ``min_pairs``) from its translations.  A row that ``depth_align`` could not move (its ok is 0) goes to the ICP with the pose it had.
+    Returns ``icp_refine``'s dict plus ``align``: the dict of ``depth_align``."""
+    _gates(dist_gate, normal_gate)   # both steps' scalars are judged before either runs
+    if int(iters) < 0 or int(min_pairs) < 6:
+        raise ValueError(f"iters {iters} must be >= 0 and min_pairs {min_pairs} >= 6 (the unknowns of a pose)")
+    align = depth_align(meshes, labels, R0, t0, K, depth_scene, frame, rounds=rounds, gate=gate, min_pairs=align_min_pairs, near=near, far=far)
+    out = icp_refine(meshes, labels, R0, align["t"], K, depth_scene, frame, iters=iters, dist_gate=dist_gate, normal_gate=normal_gate,
+                     min_pairs=min_pairs, near=near, far=far)
+    out["align"] = align
     return out

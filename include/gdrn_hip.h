@@ -1252,6 +1252,45 @@ int gdrn_icp_refine(const double* verts, const int* faces, const int* vert_off, 
                     double normal_gate, int min_pairs, float* depth_ren_scratch, int* ok, int* iters_done, int* pairs, double* rms,
                     void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Coarse depth alignment in front of the refinement above (added within ABI 5: new entry points, nothing changed): every estimate is shifted
+ * along its viewing ray by the median difference between the observed and the rendered depth, so that an RGB-only estimate -- centimetres off
+ * along the ray -- comes within gdrn_icp_refine's dist_gate.  The reference has no counterpart; the entry points are pinned to geometry and to
+ * a host restatement (tests/align_host.py).  The median is an exact order statistic; only integer atomics are used: the same call gives the
+ * same bits, and the instances of a batch do not influence each other.
+ *
+ *   depth_ren, depth_scene, frame, frame_host, F: as above.  For estimate i, ren = depth_ren[i], sc = depth_scene[frame[i]], both [H][W] fp32.
+ *
+ * pair     pixel p is a pair iff ren[p] > 0, sc[p] > 0 and fabs((double)d) <= gate, d = sc[p] - ren[p] being ONE fp32 subtraction.  (NaN fails
+ *          > 0;  +inf gives d = inf, which fails the gate.)
+ * counts   covered = the number of pixels with ren > 0;  pairs = n = the number of pairs.
+ * few      n < min_pairs:  ok = 0, offset = NaN, the translation is left bit for bit.
+ * median   otherwise, with the d of the pairs in ascending order, lo = d[(n - 1) / 2], hi = d[n / 2] (integer division) and
+ *          offset = 0.5 * ((double)lo + (double)hi): numpy's median of the widened values, exactly, for odd and even n.  ok = 1.
+ * shift    in fp64, no contraction:  s = offset / t_z;  t_x += s * t_x;  t_y += s * t_y;  t_z += offset  (s from t_z before the shift).  The
+ *          model origin keeps its image;  R is not touched.
+ *
+ * gdrn_depth_offset: one evaluation on given maps: offset [N] fp64, pairs, covered, ok [N] int32.  A first launch (one workgroup per instance
+ *   and band of 16 rows) appends the order-preserving integer keys of the pairs' differences to a per-instance list in `workspace`, a second
+ *   (one workgroup per instance) selects the two ranks by radix selection over integer histograms (11 + 11 + 10 bits), a third writes the outputs.
+ * gdrn_depth_align: the mesh table, labels, near and far exactly as gdrn_render_depth takes them;  R read only, t in/out.  `rounds` times on the
+ *   one stream (a fixed count, no stop rule): gdrn_render_depth into depth_ren_scratch [N][H][W] fp32 under the current pose, the offset, the
+ *   shift.  An instance with ok = 0 in some round is frozen from then on;  ok, pairs, covered, offset are those of the instance's last
+ *   evaluated round (rounds == 0: ok 1, pairs 0, covered 0, offset NaN, the translation untouched).  Nothing is read back.
+ *   workspace (both calls): gdrn_depth_align_workspace_bytes(N, H, W) bytes of device memory, 8-byte aligned;  every call initialises what it
+ *   reads, the caller prepares nothing.
+ * Status: GDRN_ERR_ARG for N < 0, H or W < 1, H * W of 2^31 - 1024 and more, a gate that is not > 0, rounds < 0, min_pairs < 1, a label or a
+ *   frame out of range, the rasterizer's argument rules, or (N > 0) a NULL pointer or a misaligned workspace;  GDRN_ERR_SHAPE for N > 65535 and
+ *   the rasterizer's shape rules.  Everything is checked on the host before a stream or a device pointer is touched;  N == 0 launches nothing. */
+long long gdrn_depth_align_workspace_bytes(int N, int H, int W);
+int gdrn_depth_offset(const float* depth_ren, const float* depth_scene, const int* frame, const int* frame_host, int F, int N, int H, int W,
+                      double gate, int min_pairs, double* offset, int* pairs, int* covered, int* ok, void* workspace, void* stream);
+int gdrn_depth_align(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off, const int* nfaces, int C,
+                     int f_max, const int* labels, const int* labels_host, const double* R, double* t, const double* K, int N,
+                     const float* depth_scene, const int* frame, const int* frame_host, int F, int H, int W, double near, double far, int rounds,
+                     double gate, int min_pairs, float* depth_ren_scratch, int* ok, int* pairs, int* covered, double* offset, void* workspace,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
