@@ -910,6 +910,68 @@ def refine_scene(inp, depth_gt):
 
 
 # ----------------------------------------------------------------------------------------------
+# flat-faced objects for the silhouette term of the depth refinement (gdrnet_amd.refine.icp_refine_sil)
+# ----------------------------------------------------------------------------------------------
+SILHOUETTE_CASES = ("isolated", "occluded")
+SILHOUETTE_GROW = 6   # pixels the occluder reaches beyond the object's box
+SILHOUETTE_STARTS = (((0.0, 0.0, 1.0), 0.0, (3.0, 0.0, 0.0)), ((0.0, 0.0, 1.0), 3.0, (2.0, -2.0, 0.0)), ((1.0, 1.0, 0.2), 2.0, (2.0, 1.0, 2.0)),
+                     ((0.2, 1.0, 0.5), 4.0, (-4.0, 3.0, -3.0)))
+SILHOUETTE_EXTRA_START = ((1.0, 0.2, 0.1), 3.0, (4.0, 2.0, 1.0))   # "occluded" only
+
+
+def make_silhouette_inputs(case):
+    """Inputs of the silhouette term (gdrnet_amd.refine.icp_refine_sil), fp64, metres: flat-faced objects alone in 96 x 128 frames at 0.6 m under
+    K = [[600, 0, 63.5], [0, 600, 47.5], [0, 0, 1]] (a pixel's footprint is 1 mm), one ground truth per frame.  The frames and masks are not in
+    here: ``silhouette_scene(inp, depth_gt)`` composes them from renders of the ground truth.
+
+    "isolated"  ground truths 0: an 80 x 60 mm plate, fronto-parallel; 1: the plate tilted; 2: a 50 mm cube seen on two faces; 3: the cube seen
+                on three.  Four starts each (rows 4 g .. 4 g + 3), 0-4 degrees and 3-6 mm off.  Depth alone leaves 0 - 2 degenerate
+    "occluded"  ground truths 1 and 2 of "isolated", each behind a block REFINE_OCCLUDER in front of its nearest point over the left third of its
+                box, grown by SILHOUETTE_GROW pixels; five starts each
+
+    Keys: those of make_refine_inputs, and ``flat`` (the rows whose ground truth depth alone cannot refine)."""
+    if case not in SILHOUETTE_CASES:
+        raise ValueError(case)
+    H, W = 96, 128
+    K = np.array([[600.0, 0.0, 63.5], [0.0, 600.0, 47.5], [0.0, 0.0, 1.0]])
+    rot = lambda axis, deg: _axis_angle(np.array([axis], dtype=np.float64) / np.linalg.norm(axis), np.array([float(deg)]))[0]  # noqa: E731
+    vertices, faces = zip(mesh_rectangle(4, 3, xs=np.linspace(-0.04, 0.04, 5), ys=np.linspace(-0.03, 0.03, 4)), mesh_cube(0.05))
+    R_gt = np.stack([np.eye(3), rot([1, 0.3, 0], 25) @ rot([0, 0, 1], 17), rot([0, 1, 0], 40), rot([1, 0, 0], 30) @ rot([0, 1, 0], 40)])
+    gt_labels = np.array([0, 0, 1, 1], dtype=np.int64)
+    starts = list(SILHOUETTE_STARTS)
+    flat_gt = (0, 1, 2)
+    if case == "occluded":
+        R_gt, gt_labels, starts, flat_gt = R_gt[1:3], gt_labels[1:3], starts + [SILHOUETTE_EXTRA_START], (0, 1)
+    G, S = len(gt_labels), len(starts)
+    t_gt = np.array([[0.004, -0.003, 0.6]]).repeat(G, axis=0)
+    target = np.repeat(np.arange(G), S)
+    turn = np.stack([rot(a, d) for a, d, _ in starts])
+    move = 1e-3 * np.array([m for _, _, m in starts])
+    k = np.tile(np.arange(S), G)
+    return dict(vertices=list(vertices), faces=list(faces), gt_labels=gt_labels, R_gt=R_gt, t_gt=t_gt, gt_frame=np.arange(G), labels=gt_labels[target],
+                target=target, R0=turn[k] @ R_gt[target], t0=t_gt[target] + move[k], K=K[None].repeat(G * S, axis=0), frame=target.copy(),
+                start_deg=np.array([d for _, d, _ in starts])[k], start_mm=np.linalg.norm(move, axis=1)[k] * 1e3, num_frames=G, H=H, W=W,
+                near=0.01, far=6.5, occluded=tuple(range(G)) if case == "occluded" else (),
+                flat=tuple(int(r) for r in np.nonzero(np.isin(target, flat_gt))[0]), case=case)
+
+
+def silhouette_scene(inp, depth_gt):
+    """(frames [F,H,W] fp32, masks [G,H,W] uint8) of a make_silhouette_inputs scene from the depth maps ``depth_gt`` [G,H,W] of its ground
+    truths: the frame of an object is its render, its mask the render > 0; for a ground truth in ``occluded`` a block REFINE_OCCLUDER in front of
+    its nearest point covers the left third of its box, grown by SILHOUETTE_GROW pixels on the three outer sides, and the mask is the visible part."""
+    depth_gt = np.asarray(depth_gt, dtype=np.float32)
+    frames, masks = depth_gt.copy(), (depth_gt > 0).astype(np.uint8)
+    H, W = depth_gt.shape[1:]
+    for g in inp["occluded"]:
+        ys, xs = np.nonzero(depth_gt[g] > 0)
+        x1, x2, g6 = int(xs.min()), int(xs.max()), SILHOUETTE_GROW
+        box = (slice(max(int(ys.min()) - g6, 0), min(int(ys.max()) + 1 + g6, H)), slice(max(x1 - g6, 0), x1 + (x2 - x1 + 1) // 3))
+        frames[g][box] = np.float32(np.float64(depth_gt[g][depth_gt[g] > 0].min()) - REFINE_OCCLUDER)
+        masks[g][box] = 0
+    return frames, masks
+
+
+# ----------------------------------------------------------------------------------------------
 # estimates of the YCB-V score tables (gdrnet_amd.sixd_scores, golden G18)
 # ----------------------------------------------------------------------------------------------
 SIXD_SCORE_SEEDS = {"sym": 191}

@@ -1291,6 +1291,63 @@ int gdrn_depth_align(const double* verts, const int* faces, const int* vert_off,
                      double gate, int min_pairs, float* depth_ren_scratch, int* ok, int* pairs, int* covered, double* offset, void* workspace,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Silhouette term for the depth refinement above (added within ABI 5: new entry points, nothing changed): the contour of the observed instance
+ * mask constrains the directions the point-to-plane term cannot see -- a plate slides in its plane, a cube seen on two faces along their
+ * common edge, and gdrn_icp_refine marks such rows DEGENERATE.  The reference has no counterpart; the entry points are pinned to geometry, to
+ * an exact Euclidean distance transform and to the reference's edge rule (lib/utils/mask_utils.get_edge, bw = 1) through a host restatement
+ * (tests/sil_host.py).  The transform is exact in integers; the sums are fp64, contraction off, in the fixed order of the section above; only
+ * integer atomics are used: the same call gives the same bits, and the instances of a batch do not influence each other.
+ *
+ *   mask_obs [N][H][W] uint8: the observed instance mask of each estimate in its frame, nonzero = object.  depth_ren, depth_scene, frame,
+ *   frame_host, F, K and the rays d(x, y) as above;  zs = depth_scene[frame[i]], zr = depth_ren[i].
+ *
+ * observed contour   pixel p with mask_obs[p] != 0 is a contour pixel iff some in-frame 4-neighbour q has mask_obs[q] == 0 (the frame border is
+ *           no edge), unless for any such q:  zs[q] > 0 && zs[p] > 0 && zs[q] < zs[p]  (fp32 compares) -- that is an occluder's boundary,
+ *           not the object's.
+ * transform d2[p] (int32) = the minimum over the contour pixels c of the instance of (cx - px)^2 + (cy - py)^2, exactly;  nearest[p] (int32) =
+ *           cy * W + cx of the minimiser with the smallest linear index;  without a contour pixel d2 = INT32_MAX and nearest = -1.
+ *           contour [N] int32 = the number of contour pixels.
+ * rendered contour   pixel p is on it when zr[p] > 0, some in-frame 4-neighbour has !(zr > 0), and it is not hidden in the observation:
+ *           not (zs[p] > 0 && (double)zs[p] < (double)zr[p] - dist_gate).
+ * pair      a rendered contour pixel with nearest[p] >= 0 and (double)d2[p] <= sil_gate * sil_gate (sil_gate in pixels, > 0).
+ * system    point to ray: the model point must come to lie on the ray of its observed contour pixel c = nearest[p].  z = (double)zr[p], d = d(p),
+ *           g = d(c), P = (z dx, z dy, z);  n1 = (1, 0, -gx), n2 = (0, 1, -gy);  r1 = z (dx - gx), r2 = z (dy - gy), in metres;
+ *           J_k = [P x n_k, n_k] (rotation first, the cross product written out in full);  A = sum J_1 J_1^T + J_2 J_2^T, b = sum J_1 r1 + J_2 r2,
+ *           sq = sum r1^2 + r2^2 (a pixel's k = 1 term before its k = 2 term), pairs = the number of pair pixels;  sys [N][28] as above.
+ * combined  entry by entry sys = sys_depth + weight * sys_sil (one multiply, one add), pairs = pairs_depth + pairs_sil;  the DEGENERATE / solve /
+ *           update / CONVERGED rules of gdrn_icp_step then apply unchanged.
+ *
+ * gdrn_sil_contour_transform: d2, nearest [N][H][W] int32 and contour [N] int32 of the masks.  Three launches: the contour bytes, a column
+ *   pass (the nearest contour pixel above and below), a row pass (the minimum of (x - x')^2 + g(x')^2 with the row's g in LDS, tiled for any W).
+ * gdrn_sil_accumulate: one accumulation on given renders and a given transform: sys [N][28] fp64 and pairs [N] int32.  One workgroup per
+ *   (instance, band of 16 rows) writes its slab into `workspace`; a second launch combines the bands in ascending order.
+ * gdrn_icp_step_sil: the combined step from combined systems;  R, t, state as for gdrn_icp_step.
+ * gdrn_icp_refine_sil: the arguments of gdrn_icp_refine plus mask_obs, sil_weight, sil_gate.  The transform once;  then `iters` times on the
+ *   one stream: gdrn_render_depth into depth_ren_scratch, gdrn_icp_accumulate, the silhouette accumulate pass, the combined step -- which
+ *   combines the silhouette slabs in its prologue with the operation sequence of gdrn_sil_accumulate's second launch: the same bits.  Nothing
+ *   is read back.  Outputs, per instance: ok, iters_done as for gdrn_icp_refine;  pairs and rms = sqrt(sq / pairs) of the depth term,
+ *   sil_pairs [N] int32 and sil_rms [N] fp64 = sqrt(sq_sil / pairs_sil) of the silhouette term (metres), all of the last systems accumulated
+ *   while the instance was running (NaN without a pair;  iters == 0: ok 1, counts 0, both rms NaN, the pose untouched, nothing but that written).
+ *   workspace (all calls): gdrn_sil_workspace_bytes(N, H, W) bytes of device memory, 8-byte aligned, no initialisation needed.
+ * Status: the rules of gdrn_icp_refine, and GDRN_ERR_ARG for a sil_gate that is not > 0 or a weight that is not finite and >= 0;
+ *   GDRN_ERR_SHAPE for H or W > 16384 (so that d2 fits) and N > 65535.  Everything is checked on the host before a stream or a device pointer
+ *   is touched;  N == 0 launches nothing. */
+long long gdrn_sil_workspace_bytes(int N, int H, int W);
+int gdrn_sil_contour_transform(const unsigned char* mask_obs, const float* depth_scene, const int* frame, const int* frame_host, int F, int N, int H,
+                               int W, int* d2, int* nearest, int* contour, void* workspace, void* stream);
+int gdrn_sil_accumulate(const float* depth_ren, const float* depth_scene, const int* frame, const int* frame_host, int F, const double* K,
+                        const int* d2, const int* nearest, int N, int H, int W, double sil_gate, double dist_gate, double* sys, int* pairs,
+                        void* workspace, void* stream);
+int gdrn_icp_step_sil(const double* sys_depth, const int* pairs_depth, const double* sys_sil, const int* pairs_sil, double weight, int N,
+                      int min_pairs, double* R, double* t, int* state, void* stream);
+int gdrn_icp_refine_sil(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off, const int* nfaces,
+                        int C, int f_max, const int* labels, const int* labels_host, double* R, double* t, const double* K, int N,
+                        const float* depth_scene, const int* frame, const int* frame_host, int F, const unsigned char* mask_obs, int H, int W,
+                        double near, double far, int iters, double dist_gate, double normal_gate, int min_pairs, double sil_weight,
+                        double sil_gate, float* depth_ren_scratch, int* ok, int* iters_done, int* pairs, double* rms, int* sil_pairs,
+                        double* sil_rms, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
