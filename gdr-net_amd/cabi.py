@@ -303,13 +303,17 @@ _SIGS = {
     "gdrn_sil_accumulate": [P, P, P, P, I, P, P, P, I, I, I, D, D, P, P, P, P],
     "gdrn_icp_step_sil": [P, P, P, P, D, I, I, P, P, P, P],
     "gdrn_icp_refine_sil": [P, P, P, P, P, P, I, I, P, P, P, P, P, I, P, P, P, I, P, I, I, D, D, I, D, D, I, D, D, P, P, P, P, P, P, P, P, P],
+    "gdrn_backproject_points": [P, P, P, P, P, P, I, I, I, P, I, I, P, P, P, P],
+    "gdrn_rigid_workspace_bytes": [I, I, I],
+    "gdrn_rigid_ransac": [P, P, P, I, I, D, I, C.c_ulonglong, P, P, P, P, P, P, P, P],
+    "gdrn_rigid_fit": [P, P, P, I, I, P, P, P, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []
 _RET_LL = ("gdrn_workspace_bytes", "gdrn_pose_metrics_workspace_bytes", "gdrn_pnp_workspace_bytes", "gdrn_vsd_workspace_bytes",
            "gdrn_mssd_mspd_workspace_bytes", "gdrn_model_prep_workspace_bytes", "gdrn_ad_errors_workspace_bytes",
            "gdrn_sym_errors_workspace_bytes", "gdrn_cou_maps_workspace_bytes", "gdrn_icp_workspace_bytes",
-           "gdrn_depth_align_workspace_bytes", "gdrn_sil_workspace_bytes")
+           "gdrn_depth_align_workspace_bytes", "gdrn_sil_workspace_bytes", "gdrn_rigid_workspace_bytes")
 EXPORTS = tuple(_SIGS.keys())
 _libs = {}
 

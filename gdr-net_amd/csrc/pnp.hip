@@ -14,6 +14,7 @@
 // (The file has no 16-bit code: both library builds compile the same thing.)
 #include "common.h"
 #include "geom64.h"
+#include "ransac_draw.h"
 #include "../../include/gdrn_hip.h"
 
 namespace {
@@ -21,43 +22,11 @@ namespace {
 constexpr int PNP_THREADS = 256;
 constexpr int PNP_HYP = 256;          // hypotheses per pass over the points (their 3x4 projection matrices: 24 KB of LDS)
 constexpr int PNP_WIN = 16;           // doubles per RoI in the workspace: R (9), t (3), the winner's count, padding
-constexpr int PNP_MAX_DRAWS = 64;     // draws a hypothesis may spend on its 4 distinct indices before it counts as degenerate
 constexpr double PNP_STEP_TOL = 1e-10;
 
 template <typename T> struct PnpTile;                                   // points per LDS tile: 20 KB either way
 template <> struct PnpTile<float> { static constexpr int N = 1024; };
 template <> struct PnpTile<double> { static constexpr int N = 512; };
-
-#define PNP_HD __host__ __device__ __forceinline__
-
-PNP_HD unsigned long long pnp_mix64(unsigned long long x) {   // splitmix64 finaliser
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// draw `d` of hypothesis h of RoI n: an index below count.  No state: a function of (seed, n, h, d) alone.
-PNP_HD int pnp_draw(unsigned long long seed, int n, int h, int d, int count) {
-    const unsigned long long key = seed * 0x9E3779B97F4A7C15ull + (unsigned long long)n * 0xBF58476D1CE4E5B9ull +
-                                   (unsigned long long)h * 0x94D049BB133111EBull + (unsigned long long)d * 0xD6E8FEB86659FD93ull;
-    return (int)(((pnp_mix64(key) >> 32) * (unsigned long long)count) >> 32);
-}
-
-// 4 distinct indices below count (count >= 4): a collision advances the draw counter
-PNP_HD bool pnp_sample4(unsigned long long seed, int n, int h, int count, int* idx) {
-    int d = 0;
-    for (int k = 0; k < 4; ++k) {
-        bool found = false;
-        while (!found && d < PNP_MAX_DRAWS) {
-            const int c = pnp_draw(seed, n, h, d++, count);
-            found = true;
-            for (int j = 0; j < k; ++j) found = found && (idx[j] != c);
-            if (found) idx[k] = c;
-        }
-        if (!found) return false;
-    }
-    return true;
-}
 
 PNP_HD void pnp_cross(const double* a, const double* b, double* c) {
     c[0] = a[1] * b[2] - a[2] * b[1];
@@ -260,7 +229,7 @@ template <typename T>
 PNP_HD bool pnp_hypothesis(const T* img, const T* mod, int count, const double* K, const double* Ki, unsigned long long seed, int n, int h,
                            double* R, double* t) {
     int idx[4];
-    if (!pnp_sample4(seed, n, h, count, idx)) return false;
+    if (!pnp_sample<4>(seed, n, h, count, idx)) return false;
     double P[9], f[9], X4[3];
     for (int s = 0; s < 3; ++s) {
         const double u = (double)img[(size_t)idx[s] * 2], v = (double)img[(size_t)idx[s] * 2 + 1];

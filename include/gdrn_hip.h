@@ -1348,6 +1348,57 @@ int gdrn_icp_refine_sil(const double* verts, const int* faces, const int* vert_o
                         double sil_gate, float* depth_ren_scratch, int* ok, int* iters_done, int* pairs, double* rms, int* sil_pairs,
                         double* sil_rms, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pose from depth and object-coordinate maps: batched 3D-3D RANSAC (added within ABI 5: new entry points, nothing changed).  The RGB-D
+ * counterpart of gdrn_pnp_ransac: the network's per-pixel model point and the depth frame's camera point of the same pixel are a 3D-3D pair, and
+ * the pose follows from such pairs in closed form inside a RANSAC -- no render, no iteration; rotation, lateral position and depth are fixed
+ * together, which gives gdrn_depth_align / gdrn_icp_refine a start that is right in all six degrees of freedom.  The reference is RGB-only
+ * (WITH_DEPTH = False) and has no counterpart; the entry points are pinned to geometry and to an independent fp64 host restatement
+ * (tests/rigid_host.py).  One workgroup per RoI, all pose arithmetic fp64, sums in a fixed order (wave tree, then the waves through LDS), integer
+ * atomics on LDS only: the same call gives the same bits, and the RoIs of a batch do not influence each other.  No call allocates or reads
+ * anything back.
+ *
+ * gdrn_backproject_points.  img_pts [N][stride][2] pixels, model_pts [N][stride][3], fp32, and counts [N] int32 on the device: what
+ *   gdrn_correspondences writes.  depth [F][H][W] fp32 in metres, 0 = no measurement;  frame [N] int32 (frame_host: the same N values in host
+ *   memory, checked against [0, F) before anything is launched);  K [N][3][3] fp64.  Row j < min(max(counts[n], 0), stride) of RoI n, with (u, v)
+ *   widened exactly, looks up the NEAREST pixel ix = floor(u + 0.5), iy = floor(v + 0.5) (no bilinear sampling: it would invent depths across
+ *   edges) and is VALID iff u, v and its three model coordinates are finite, 0 <= ix < W, 0 <= iy < H, and d = depth[frame[n]][iy][ix] is finite
+ *   and > 0.  Its camera point is the point of the ray K^-1 (u, v, 1)^T -- of the correspondence's own (u, v), as PnP uses it, not of the pixel
+ *   centre -- whose z is d (a ray without a finite such point is not valid).  A singular or non-finite K[n] makes every row of RoI n invalid.
+ *   cam, mod [N][stride][3] fp64: the valid rows of RoI n compacted to the front IN THEIR INPUT ORDER (ballot + prefix scan, no atomics), the
+ *   model point widened exactly;  counts_out[n] of them, every row behind them NaN.
+ * gdrn_rigid_ransac.  cam, mod as above;  counts [N] int32 ON THE DEVICE ONLY, clamped to [0, stride] on the device: unlike gdrn_pnp_* this call
+ *   takes NO host copy of the counts, so that it chains behind gdrn_backproject_points without a read-back.  dist_thr in metres.
+ *   Sampling: the draw rule of gdrn_pnp_ransac (the same mix64, the same four multipliers, index = ((x >> 32) * counts[n]) >> 32), keeping the
+ *   first 3 distinct indices (a collision advances d; after 64 draws the hypothesis is dropped).
+ *   Closed form (the minimal sample and every refit): the proper rotation (det +1, also for a reflected optimum) and the translation minimising
+ *   sum |R m + t - c|^2 -- centroids, the cross-covariance S = sum (m - mbar)(c - cbar)^T about them, the rotation as the eigenvector of the
+ *   largest eigenvalue of Horn's symmetric 4x4 matrix of S (cyclic Jacobi, a fixed 6 sweeps), t = cbar - R mbar.
+ *   Degenerate: with s1 >= s2 >= s3 >= 0 the singular values of S and s = sign(det S), iff s2 + s s3 <= 1e-9 s1 -- evaluated as the gap between
+ *   the two largest eigenvalues of the 4x4 being <= 2e-9 s1 (they add up to 2 s1).  Collinear sets and repeated points are degenerate, coplanar
+ *   ones (s3 = 0) are not.  1e-9 is a design constant: seven digits above the fp64 rounding of the sums.  A degenerate sample scores 0.
+ *   Scoring: inliers are the rows with |R m + t - c|^2 < dist_thr^2, counted as integers.  Selection: the highest count wins, ties go to the
+ *   lowest h;  the winner needs >= 3 inliers.  Then, in gdrn_pnp_ransac's order: the closed form on the winner's inliers, the inliers
+ *   re-selected under it, the closed form once more.  inlier_mask [N][stride] u8 (or NULL), num_inliers [N] and rms [N] (or NULL; root of the
+ *   inliers' mean squared 3D distance, metres) are those of the returned pose.
+ *   R [N][3][3], t [N][3] fp64 are in/out: a RoI with fewer than 3 rows, without a non-degenerate hypothesis of >= 3 inliers, with a degenerate
+ *   refit, fewer than 3 inliers under a refit or a non-finite result keeps the caller's values bit for bit and gets ok[n] = 0, num_inliers 0, an
+ *   all-zero mask and rms NaN;  every other one ok[n] = 1.
+ *   workspace: gdrn_rigid_workspace_bytes(N, stride, iters) bytes of device memory, 8-byte aligned, no initialisation needed.
+ * gdrn_rigid_fit: the closed form over all counts[n] rows without a gate (the analogue of gdrn_pnp_refine);  rms over all of them.  The same
+ *   degeneracy rule;  an unsolved RoI (fewer than 3 rows, degenerate, a non-finite row) keeps the caller's pose, ok 0, rms NaN.  No workspace.
+ * Status: GDRN_ERR_ARG for a NULL pointer that is not nullable, N, stride, iters, F, H or W < 1, a dist_thr that is not finite and > 0, a frame
+ *   out of range;  GDRN_ERR_SHAPE for H * W or stride * 3 of 2^31 and more.  Checked on the host before anything is launched. */
+int gdrn_backproject_points(const float* img_pts, const float* model_pts, const int* counts, const float* depth, const int* frame,
+                            const int* frame_host, int F, int H, int W, const double* K, int N, int stride, double* cam, double* mod,
+                            int* counts_out, void* stream);
+long long gdrn_rigid_workspace_bytes(int N, int stride, int iters);
+int gdrn_rigid_ransac(const double* cam, const double* mod, const int* counts, int N, int stride, double dist_thr, int iters,
+                      unsigned long long seed, double* R, double* t, int* ok, int* num_inliers, unsigned char* inlier_mask, double* rms,
+                      void* workspace, void* stream);
+int gdrn_rigid_fit(const double* cam, const double* mod, const int* counts, int N, int stride, double* R, double* t, int* ok, double* rms,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
