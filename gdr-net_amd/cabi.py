@@ -155,6 +155,14 @@ def to_device_table(structs, device):
     return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
 
 
+# the argument groups the render entry points and the loops that render per iteration share (include/gdrn_hip.h)
+_MESH = [P, P, P, P, P, P, I, I]       # verts, faces, vert_off, nverts, face_off, nfaces, C, f_max
+_ROWS = [P, P, P, P, P, I]             # labels, labels_host, R, t, K, N
+_SCENE = [P, P, P, I]                  # depth_scene, frame, frame_host, F
+_FRAME = [I, I, D, D]                  # H, W, near, far
+_RENDER = _MESH + _ROWS + _FRAME + [P, P]   # ... the output map, stream
+_LOOP = _MESH + _ROWS + _SCENE + _FRAME     # the renderer's own list with the scene behind N: what the three loops start with
+
 # name -> argtypes (all return int status, except the two tile queries which return ints too, and the byte counts of _RET_LL: long long)
 _SIGS = {
     "gdrn_version": [],
@@ -260,7 +268,7 @@ _SIGS = {
     "gdrn_pnp_refine": [P, P, P, P, P, I, I, I, P, P, P, P, P, P],
     "gdrn_pnp_ransac_f64": [P, P, P, P, P, I, I, D, I, C.c_ulonglong, I, P, P, P, P, P, P, P, P],
     "gdrn_pnp_refine_f64": [P, P, P, P, P, I, I, I, P, P, P, P, P, P],
-    "gdrn_render_depth": [P, P, P, P, P, P, I, I, P, P, P, P, P, I, I, I, D, D, P, P],
+    "gdrn_render_depth": list(_RENDER),
     "gdrn_xyz_from_depth": [P, P, P, P, I, I, I, P, P, P, P, P],
     "gdrn_vsd_workspace_bytes": [I, I, I, I],
     "gdrn_vsd": [P, P, P, P, P, I, P, P, I, I, I, D, P, I, I, I, P, P, P, P],
@@ -285,7 +293,7 @@ _SIGS = {
     "gdrn_scene_gt_canvas": [P, I, I, I, I, I, P, P, P, P],
     "gdrn_scene_gt_compose": [P, P, P, P, P, I, I, I, I, P, P],
     "gdrn_scene_gt_visibility": [P, P, P, P, I, P, I, I, I, D, I, P, P, P, P, P, P, P, P, P],
-    "gdrn_render_visibility": [P, P, P, P, P, P, I, I, P, P, P, P, P, I, I, I, D, D, P, P],
+    "gdrn_render_visibility": list(_RENDER),
     "gdrn_shade_frames": [P, P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P],
     "gdrn_shade_frames_tex": [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, I, I, P, P, P, P, P, P, P],
     "gdrn_cou_maps_workspace_bytes": [I],
@@ -294,15 +302,16 @@ _SIGS = {
     "gdrn_icp_workspace_bytes": [I, I, I],
     "gdrn_icp_accumulate": [P, P, P, P, I, P, I, I, I, D, D, P, P, P, P],
     "gdrn_icp_step": [P, P, I, I, P, P, P, P],
-    "gdrn_icp_refine": [P, P, P, P, P, P, I, I, P, P, P, P, P, I, P, P, P, I, I, I, D, D, I, D, D, I, P, P, P, P, P, P, P],
+    "gdrn_icp_refine": _LOOP + [I, D, D, I] + [P] * 7,   # iters, the two gates, min_pairs | scratch, 4 outputs, workspace, stream
     "gdrn_depth_align_workspace_bytes": [I, I, I],
     "gdrn_depth_offset": [P, P, P, P, I, I, I, I, D, I, P, P, P, P, P, P],
-    "gdrn_depth_align": [P, P, P, P, P, P, I, I, P, P, P, P, P, I, P, P, P, I, I, I, D, D, I, D, I, P, P, P, P, P, P, P],
+    "gdrn_depth_align": _LOOP + [I, D, I] + [P] * 7,   # rounds, gate, min_pairs | scratch, 4 outputs, workspace, stream
     "gdrn_sil_workspace_bytes": [I, I, I],
     "gdrn_sil_contour_transform": [P, P, P, P, I, I, I, I, P, P, P, P, P],
     "gdrn_sil_accumulate": [P, P, P, P, I, P, P, P, I, I, I, D, D, P, P, P, P],
     "gdrn_icp_step_sil": [P, P, P, P, D, I, I, P, P, P, P],
-    "gdrn_icp_refine_sil": [P, P, P, P, P, P, I, I, P, P, P, P, P, I, P, P, P, I, P, I, I, D, D, I, D, D, I, D, D, P, P, P, P, P, P, P, P, P],
+    # (mask_obs sits between the scene and H) icp_refine's scalars, sil_weight, sil_gate | scratch, 6 outputs, workspace, stream
+    "gdrn_icp_refine_sil": _MESH + _ROWS + _SCENE + [P] + _FRAME + [I, D, D, I, D, D] + [P] * 9,
     "gdrn_backproject_points": [P, P, P, P, P, P, I, I, I, P, I, I, P, P, P, P],
     "gdrn_rigid_workspace_bytes": [I, I, I],
     "gdrn_rigid_ransac": [P, P, P, I, I, D, I, C.c_ulonglong, P, P, P, P, P, P, P, P],

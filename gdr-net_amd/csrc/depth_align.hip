@@ -30,6 +30,8 @@
 
 #pragma clang fp contract(off)
 
+#include "render_loop.h"
+
 namespace {
 
 constexpr int DA_THREADS = 256;
@@ -293,21 +295,20 @@ extern "C" int gdrn_depth_align(const double* verts, const int* faces, const int
                                 const double* K, int N, const float* depth_scene, const int* frame, const int* frame_host, int F, int H, int W,
                                 double near, double far, int rounds, double gate, int min_pairs, float* depth_ren_scratch, int* ok, int* pairs,
                                 int* covered, double* offset, void* workspace, void* stream) {
-    if (!da_frame_ok(N, H, W) || F < 0 || rounds < 0 || min_pairs < 1 || !(gate > 0.0)) return GDRN_ERR_ARG;
-    if (C <= 0 || f_max <= 0 || !(near > 0.0) || !(near < far)) return GDRN_ERR_ARG;
+    const RenderRows rows = {verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far};
+    const RenderScene scene = {depth_scene, frame, frame_host, F};
+    if (!da_frame_ok(N, H, W) || rounds < 0 || min_pairs < 1 || !(gate > 0.0)) return GDRN_ERR_ARG;
+    if (!loop_scalars_ok(rows, scene)) return GDRN_ERR_ARG;
     if (N == 0) return GDRN_OK;
-    if (!verts || !faces || !vert_off || !nverts || !face_off || !nfaces || !labels || !labels_host || !R || !t || !K || !depth_scene || !frame ||
-        !frame_host || !depth_ren_scratch || !ok || !pairs || !covered || !offset || !workspace || ((size_t)workspace & 7))
-        return GDRN_ERR_ARG;
-    if (N > 65535) return GDRN_ERR_SHAPE;
-    if (!host_in_range(labels_host, N, C) || !host_in_range(frame_host, N, F)) return GDRN_ERR_ARG;
+    if (!depth_ren_scratch || !ok || !pairs || !covered || !offset || !workspace || ((size_t)workspace & 7)) return GDRN_ERR_ARG;
+    int bad = loop_rows_check(rows, scene);
+    if (bad != GDRN_OK) return bad;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const DaWs w = da_carve(workspace, N);
     GDRN_LAUNCH(da_init_kernel, dim3(cdiv(N, DA_THREADS)), dim3(DA_THREADS), 0, st, N, w.state, ok, pairs, covered, offset);
     GDRN_CHECK_LAUNCH();
     for (int r = 0; r < rounds; ++r) {
-        int bad = gdrn_render_depth(verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far,
-                                    depth_ren_scratch, stream);
+        bad = render_into(rows, depth_ren_scratch, stream);
         if (bad != GDRN_OK) return bad;
         bad = da_launch_offset(depth_ren_scratch, depth_scene, frame, F, N, H, W, gate, min_pairs, t, w.state, ok, pairs, covered, offset, w, st);
         if (bad != GDRN_OK) return bad;

@@ -25,16 +25,12 @@
 #pragma clang fp contract(off)
 
 #include "raster64.h"
-#include "icp_step.h"
+#include "icp_shared.h"
+#include "render_loop.h"
 
 namespace {
 
-constexpr int ICP_THREADS = 256;
-constexpr int ICP_WAVES = ICP_THREADS / 64;
-constexpr int ICP_BAND_ROWS = 16;               // rows of one workgroup's band
 constexpr int ICP_PPT = 4;                      // render depths a lane loads before it looks at any of them
-
-__host__ __device__ __forceinline__ int icp_bands(int H) { return (H + ICP_BAND_ROWS - 1) / ICP_BAND_ROWS; }
 
 // Workgroup (band, instance): pixels [y0 * W, y1 * W) of the instance's render.  sums [N][nb][28] fp64, cnts [N][nb] int32.
 __global__ __launch_bounds__(ICP_THREADS) void icp_accumulate_kernel(const float* __restrict__ depth_ren, const float* __restrict__ depth_scene,
@@ -104,46 +100,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_accumulate_kernel(const float
             }
         }
     }
-    // the count first: a band without a pair (most of a frame) writes its zeros without the fold
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n_pairs += __shfl_xor(n_pairs, o, 64);
-    if ((tid & 63) == 0) red_n[tid >> 6] = n_pairs;
-    __syncthreads();
-    const int total = (red_n[0] + red_n[1]) + (red_n[2] + red_n[3]);
-    double* slab = sums + ((size_t)i * nb + band) * ICP_SUMS;
-    if (tid == 0) cnts[(size_t)i * nb + band] = total;
-    if (total == 0) {   // uniform over the workgroup
-        if (tid < ICP_SUMS) slab[tid] = 0.0;
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < ICP_SUMS; ++k) {
-        const double s = wave_sum_f64(acc[k]);
-        if ((tid & 63) == 0) red[tid >> 6][k] = s;
-    }
-    __syncthreads();
-    if (tid < ICP_SUMS) slab[tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-}
-
-// behind a stand-alone accumulate: the slabs into sys [N][28] and pairs [N]; one wave per instance
-__global__ __launch_bounds__(64) void icp_combine_kernel(const double* __restrict__ sums, const int* __restrict__ cnts, int nb,
-                                                          double* __restrict__ sys, int* __restrict__ pairs) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (lane < ICP_SUMS) sys[(size_t)i * ICP_SUMS + lane] = icp_combine(sums, i, nb, lane);
-    else if (lane == ICP_SUMS) pairs[i] = icp_combine_n(cnts, i, nb);
-}
-
-// the defaults of an instance no system was accumulated for (iters == 0), and the running state
-__global__ __launch_bounds__(ICP_THREADS) void icp_init_kernel(int N, int* __restrict__ state, int* __restrict__ ok, int* __restrict__ iters_done,
-                                                                int* __restrict__ pairs, double* __restrict__ rms) {
-    const int i = blockIdx.x * ICP_THREADS + threadIdx.x;
-    if (i >= N) return;
-    state[(size_t)i * 2 + 0] = GDRN_ICP_RUNNING;
-    state[(size_t)i * 2 + 1] = 0;
-    ok[i] = 1;
-    iters_done[i] = 0;
-    pairs[i] = 0;
-    rms[i] = __longlong_as_double(0x7ff8000000000000LL);
+    icp_fold_band(acc, n_pairs, red, red_n, i, band, nb, sums, cnts);
 }
 
 // One wave per instance.  Prologue: the instance's sums over its nb bands (nb = 1: a combined system as it is).  A frozen instance (state != running)
@@ -233,22 +190,22 @@ extern "C" int gdrn_icp_refine(const double* verts, const int* faces, const int*
                                const double* K, int N, const float* depth_scene, const int* frame, const int* frame_host, int F, int H, int W,
                                double near, double far, int iters, double dist_gate, double normal_gate, int min_pairs, float* depth_ren_scratch,
                                int* ok, int* iters_done, int* pairs, double* rms, void* workspace, void* stream) {
-    if (!icp_frame_ok(N, H, W) || F < 0 || iters < 0 || min_pairs < 6 || !(dist_gate > 0.0) || !(normal_gate > 0.0)) return GDRN_ERR_ARG;
-    if (C <= 0 || f_max <= 0 || !(near > 0.0) || !(near < far)) return GDRN_ERR_ARG;
+    const RenderRows rows = {verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far};
+    const RenderScene scene = {depth_scene, frame, frame_host, F};
+    if (!icp_frame_ok(N, H, W) || iters < 0 || min_pairs < 6 || !(dist_gate > 0.0) || !(normal_gate > 0.0)) return GDRN_ERR_ARG;
+    if (!loop_scalars_ok(rows, scene)) return GDRN_ERR_ARG;
     if (N == 0) return GDRN_OK;
-    if (!verts || !faces || !vert_off || !nverts || !face_off || !nfaces || !labels || !labels_host || !R || !t || !K || !depth_scene || !frame ||
-        !frame_host || !depth_ren_scratch || !ok || !iters_done || !pairs || !rms || !workspace || ((size_t)workspace & 7))
-        return GDRN_ERR_ARG;
-    if (N > 65535) return GDRN_ERR_SHAPE;
-    if (!host_in_range(labels_host, N, C) || !host_in_range(frame_host, N, F)) return GDRN_ERR_ARG;
+    if (!depth_ren_scratch || !ok || !iters_done || !pairs || !rms || !workspace || ((size_t)workspace & 7)) return GDRN_ERR_ARG;
+    int bad = loop_rows_check(rows, scene);
+    if (bad != GDRN_OK) return bad;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nb = icp_bands(H);
     const IcpWs w = icp_carve(workspace, N, nb);
-    GDRN_LAUNCH(icp_init_kernel, dim3(cdiv(N, ICP_THREADS)), dim3(ICP_THREADS), 0, st, N, w.state, ok, iters_done, pairs, rms);
+    GDRN_LAUNCH(icp_init_kernel, dim3(cdiv(N, ICP_THREADS)), dim3(ICP_THREADS), 0, st, N, w.state, ok, iters_done, pairs, rms, (int*)nullptr,
+                (double*)nullptr);
     GDRN_CHECK_LAUNCH();
     for (int it = 0; it < iters; ++it) {
-        int bad = gdrn_render_depth(verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far,
-                                    depth_ren_scratch, stream);
+        bad = render_into(rows, depth_ren_scratch, stream);
         if (bad != GDRN_OK) return bad;
         bad = icp_launch_accumulate(depth_ren_scratch, depth_scene, frame, F, K, N, H, W, dist_gate, normal_gate, w, st);
         if (bad != GDRN_OK) return bad;

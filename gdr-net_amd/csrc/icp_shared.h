@@ -1,16 +1,50 @@
-// The solve-and-update step of the depth refinement, shared by csrc/icp.hip and csrc/silhouette.hip: one copy of the band combine and of the rules
-// stated with gdrn_icp_step in include/gdrn_hip.h.  Included behind `#pragma clang fp contract(off)`: the operation sequence is the contract.
+// What the depth refinement's passes share (csrc/icp.hip, csrc/silhouette.hip): the launch shape of an accumulate pass, its band fold, the band
+// combine with the kernel behind a stand-alone accumulate, the init kernel of a loop, and the solve-and-update step with the rules stated with
+// gdrn_icp_step in include/gdrn_hip.h.  Included behind `#pragma clang fp contract(off)`: the operation sequence is the contract.
 #pragma once
 
 namespace {
 
+constexpr int ICP_THREADS = 256;
+constexpr int ICP_WAVES = ICP_THREADS / 64;
+constexpr int ICP_BAND_ROWS = 16;               // rows of one workgroup's band
 constexpr int ICP_SUMS = 28;                    // 21 of A (packed upper, row-major), 6 of b, 1 of sq
 constexpr double ICP_PIVOT_MIN = 1e-9;          // smallest accepted Cholesky pivot of the Jacobi-scaled matrix
 constexpr double ICP_STEP_TOL = 1e-10;          // the PnP refinement's stop rule
 constexpr double ICP_SMALL_ANGLE = 1e-12;       // below: exp(w) = I + [w]x
 
+__host__ __device__ __forceinline__ int icp_bands(int H) { return (H + ICP_BAND_ROWS - 1) / ICP_BAND_ROWS; }
+
 // index of (i, j), i <= j, in the packed upper triangle of a 6x6
 __host__ __device__ __forceinline__ int icp_tri(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
+
+// The end of an accumulate pass, called by every lane of workgroup (band, instance i) with its 28 sums and its pair count: the slab
+// sums[i][band][28] and cnts[i][band] in a fixed order (xor tree per wave, four waves in LDS).  The count first: a band without a pair (most of a
+// frame) writes its zeros without the fold.
+__device__ __forceinline__ void icp_fold_band(const double (&acc)[ICP_SUMS], int n_pairs, double (&red)[ICP_WAVES][ICP_SUMS],
+                                              int (&red_n)[ICP_WAVES], int i, int band, int nb, double* __restrict__ sums,
+                                              int* __restrict__ cnts) {
+    static_assert(ICP_WAVES == 4, "the sums below name four waves");
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n_pairs += __shfl_xor(n_pairs, o, 64);
+    if ((tid & 63) == 0) red_n[tid >> 6] = n_pairs;
+    __syncthreads();
+    const int total = (red_n[0] + red_n[1]) + (red_n[2] + red_n[3]);
+    double* slab = sums + ((size_t)i * nb + band) * ICP_SUMS;
+    if (tid == 0) cnts[(size_t)i * nb + band] = total;
+    if (total == 0) {   // uniform over the workgroup
+        if (tid < ICP_SUMS) slab[tid] = 0.0;
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < ICP_SUMS; ++k) {
+        const double s = wave_sum_f64(acc[k]);
+        if ((tid & 63) == 0) red[tid >> 6][k] = s;
+    }
+    __syncthreads();
+    if (tid < ICP_SUMS) slab[tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
 
 // sum k of instance i over its bands, ascending: the one combine, wherever it runs
 __device__ __forceinline__ double icp_combine(const double* __restrict__ sums, int i, int nb, int k) {
@@ -23,6 +57,33 @@ __device__ __forceinline__ int icp_combine_n(const int* __restrict__ cnts, int i
     int v = 0;
     for (int b = 0; b < nb; ++b) v += cnts[(size_t)i * nb + b];
     return v;
+}
+
+// behind a stand-alone accumulate: the slabs into sys [N][28] and pairs [N]; one wave per instance
+__global__ __launch_bounds__(64) void icp_combine_kernel(const double* __restrict__ sums, const int* __restrict__ cnts, int nb,
+                                                          double* __restrict__ sys, int* __restrict__ pairs) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (lane < ICP_SUMS) sys[(size_t)i * ICP_SUMS + lane] = icp_combine(sums, i, nb, lane);
+    else if (lane == ICP_SUMS) pairs[i] = icp_combine_n(cnts, i, nb);
+}
+
+// the defaults of an instance no system was accumulated for (iters == 0), and the running state.  sil_pairs / sil_rms are NULL together: the
+// loop without a silhouette term
+__global__ __launch_bounds__(ICP_THREADS) void icp_init_kernel(int N, int* __restrict__ state, int* __restrict__ ok, int* __restrict__ iters_done,
+                                                                int* __restrict__ pairs, double* __restrict__ rms, int* __restrict__ sil_pairs,
+                                                                double* __restrict__ sil_rms) {
+    const int i = blockIdx.x * ICP_THREADS + threadIdx.x;
+    if (i >= N) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    state[(size_t)i * 2 + 0] = GDRN_ICP_RUNNING;
+    state[(size_t)i * 2 + 1] = 0;
+    ok[i] = 1;
+    iters_done[i] = 0;
+    pairs[i] = 0;
+    rms[i] = nan;
+    if (sil_pairs == nullptr) return;
+    sil_pairs[i] = 0;
+    sil_rms[i] = nan;
 }
 
 // xi of A xi = -b through the Cholesky factor of S A S, S = diag(A_ii^-1/2); false: degenerate (a diagonal entry <= 0 or a pivot < ICP_PIVOT_MIN,

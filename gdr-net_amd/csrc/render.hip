@@ -18,6 +18,7 @@
 #pragma clang fp contract(off)
 
 #include "raster64.h"
+#include "render_loop.h"
 
 namespace {
 
@@ -255,14 +256,13 @@ bool frame_fits(int N, int H, int W) {
     return hw <= 0x7fffffffLL - RD_THREADS && (long long)N * ((hw + RD_THREADS - 1) / RD_THREADS) <= 0x7fffffffLL;
 }
 
-// the argument rules the two rasterizer entry points share; `out` is the depth or the visibility buffer
-int raster_args(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off, const int* nfaces, int C, int f_max,
-                const int* labels, const int* labels_host, const double* R, const double* t, const double* K, int N, int H, int W, double near,
-                double far, const void* out) {
-    if (!verts || !faces || !vert_off || !nverts || !face_off || !nfaces || !labels || !labels_host || !R || !t || !K || !out) return GDRN_ERR_ARG;
-    if (!frame_ok(N, H, W) || C <= 0 || f_max <= 0 || !(near > 0.0) || !(near < far)) return GDRN_ERR_ARG;
-    if (!host_in_range(labels_host, N, C)) return GDRN_ERR_ARG;
-    if (!frame_fits(N, H, W) || cdiv(f_max, RD_THREADS) > 65535) return GDRN_ERR_SHAPE;
+// the argument rules the two rasterizer entry points share; `out` is the depth or the visibility buffer (csrc/render_loop.h states the rules
+// of the rows once, for these and for the loops that render)
+int raster_args(const RenderRows& a, const void* out) {
+    if (!rows_pointers_ok(a) || !out) return GDRN_ERR_ARG;
+    if (!frame_ok(a.N, a.H, a.W) || !rows_scalars_ok(a)) return GDRN_ERR_ARG;
+    if (!host_in_range(a.labels_host, a.N, a.C)) return GDRN_ERR_ARG;
+    if (!frame_fits(a.N, a.H, a.W) || cdiv(a.f_max, RD_THREADS) > 65535) return GDRN_ERR_SHAPE;
     return GDRN_OK;
 }
 
@@ -279,7 +279,7 @@ int raster_split(int N, int chunks) {
 extern "C" int gdrn_render_depth(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off,
                                  const int* nfaces, int C, int f_max, const int* labels, const int* labels_host, const double* R,
                                  const double* t, const double* K, int N, int H, int W, double near, double far, float* depth, void* stream) {
-    const int bad = raster_args(verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far, depth);
+    const int bad = raster_args({verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far}, depth);
     if (bad != GDRN_OK) return bad;
     const int chunks = cdiv(f_max, RD_THREADS);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -301,7 +301,7 @@ extern "C" int gdrn_render_visibility(const double* verts, const int* faces, con
                                       const int* nfaces, int C, int f_max, const int* labels, const int* labels_host, const double* R,
                                       const double* t, const double* K, int N, int H, int W, double near, double far, unsigned long long* vis,
                                       void* stream) {
-    const int bad = raster_args(verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far, vis);
+    const int bad = raster_args({verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far}, vis);
     if (bad != GDRN_OK) return bad;
     const int chunks = cdiv(f_max, RD_THREADS);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -20,8 +20,9 @@
 // smaller index: the minimum over the columns is the minimum over all contour pixels, ties included.
 //
 // The accumulate pass is the ICP's: one workgroup per (instance, band of 16 rows), 28 fp64 sums and a count per lane, folded in a fixed order
-// (xor tree per wave, four waves in LDS) into the band's slab; the slabs are combined in ascending order at the next launch boundary, by the
-// same device function in the stand-alone combine and in the step's prologue.  No floating-point atomics.
+// (xor tree per wave, four waves in LDS) into the band's slab by the ICP's own fold (csrc/icp_shared.h); the slabs are combined in ascending
+// order at the next launch boundary, by the same device function in the stand-alone combine and in the step's prologue.  No floating-point
+// atomics.
 //
 // Floating-point contraction is OFF for this file, as for icp.hip.  (No 16-bit code: both library builds compile the same thing.)
 #include <climits>
@@ -33,20 +34,17 @@
 #pragma clang fp contract(off)
 
 #include "raster64.h"
-#include "icp_step.h"
+#include "icp_shared.h"
+#include "render_loop.h"
 
 namespace {
 
-constexpr int SIL_THREADS = 256;
-constexpr int SIL_WAVES = SIL_THREADS / 64;
-constexpr int SIL_BAND_ROWS = 16;     // rows of one workgroup's band: the ICP's
+constexpr int SIL_THREADS = 256;      // lanes of a workgroup of the transform kernels (the accumulate pass has the ICP's launch shape: ICP_*)
 constexpr int SIL_TILE = 2048;        // columns of a row held in LDS at a time (8 KiB)
 constexpr int SIL_GROUP = 32;         // columns a lane skips or walks as one
 constexpr int SIL_NONE = INT_MAX;     // column offset: no contour pixel in the column
 constexpr int SIL_MAX_SIDE = 16384;   // 2 * 16383^2 < 2^31: d2 fits
 static_assert(SIL_GROUP == 32 && SIL_TILE % SIL_THREADS == 0, "a wave loads two whole groups at a time");
-
-__host__ __device__ __forceinline__ int sil_bands(int H) { return (H + SIL_BAND_ROWS - 1) / SIL_BAND_ROWS; }
 
 // grid (cdiv(H W, 256), N).  flags [N][H][W] uint8, contour [N] int32 (zeroed before the launch)
 __global__ __launch_bounds__(SIL_THREADS) void sil_contour_kernel(const unsigned char* __restrict__ mask, const float* __restrict__ depth_scene,
@@ -149,15 +147,15 @@ __global__ __launch_bounds__(SIL_THREADS) void sil_row_kernel(const int* __restr
 }
 
 // Workgroup (band, instance): pixels [y0 * W, y1 * W) of the instance's render.  sums [N][nb][28] fp64, cnts [N][nb] int32.
-__global__ __launch_bounds__(SIL_THREADS) void sil_accumulate_kernel(const float* __restrict__ depth_ren, const float* __restrict__ depth_scene,
+__global__ __launch_bounds__(ICP_THREADS) void sil_accumulate_kernel(const float* __restrict__ depth_ren, const float* __restrict__ depth_scene,
                                                                       const int* __restrict__ frame, int F, const double* __restrict__ Km,
                                                                       const int* __restrict__ d2, const int* __restrict__ nearest, int H, int W,
                                                                       double gate2, double dist_gate, double* __restrict__ sums,
                                                                       int* __restrict__ cnts) {
-    __shared__ double red[SIL_WAVES][ICP_SUMS];
-    __shared__ int red_n[SIL_WAVES];
+    __shared__ double red[ICP_WAVES][ICP_SUMS];
+    __shared__ int red_n[ICP_WAVES];
     const int band = blockIdx.x, i = blockIdx.y, nb = gridDim.x, tid = threadIdx.x;
-    const int y0 = band * SIL_BAND_ROWS, y1 = min(y0 + SIL_BAND_ROWS, H);
+    const int y0 = band * ICP_BAND_ROWS, y1 = min(y0 + ICP_BAND_ROWS, H);
     const int f = frame[i];
     double acc[ICP_SUMS];
 #pragma unroll
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(SIL_THREADS) void sil_accumulate_kernel(const float
         const int* nn = nearest + (size_t)i * H * W;
         const Cam cam = load_cam(Km + (size_t)i * 9);
         const int p1 = y1 * W;
-        for (int p = y0 * W + tid; p < p1; p += SIL_THREADS) {   // a lane's pixels in ascending order
+        for (int p = y0 * W + tid; p < p1; p += ICP_THREADS) {   // a lane's pixels in ascending order
             const float zr_f = ren[p];
             if (!(zr_f > 0.f)) continue;
             const int y = p / W, x = p - y * W;
@@ -208,50 +206,7 @@ __global__ __launch_bounds__(SIL_THREADS) void sil_accumulate_kernel(const float
             ++n_pairs;
         }
     }
-    // the count first: a band without a pair (most of a frame) writes its zeros without the fold
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n_pairs += __shfl_xor(n_pairs, o, 64);
-    if ((tid & 63) == 0) red_n[tid >> 6] = n_pairs;
-    __syncthreads();
-    const int total = (red_n[0] + red_n[1]) + (red_n[2] + red_n[3]);
-    double* slab = sums + ((size_t)i * nb + band) * ICP_SUMS;
-    if (tid == 0) cnts[(size_t)i * nb + band] = total;
-    if (total == 0) {   // uniform over the workgroup
-        if (tid < ICP_SUMS) slab[tid] = 0.0;
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < ICP_SUMS; ++k) {
-        const double s = wave_sum_f64(acc[k]);
-        if ((tid & 63) == 0) red[tid >> 6][k] = s;
-    }
-    __syncthreads();
-    if (tid < ICP_SUMS) slab[tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-}
-
-// behind a stand-alone accumulate: the slabs into sys [N][28] and pairs [N]; one wave per instance
-__global__ __launch_bounds__(64) void sil_combine_kernel(const double* __restrict__ sums, const int* __restrict__ cnts, int nb,
-                                                          double* __restrict__ sys, int* __restrict__ pairs) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (lane < ICP_SUMS) sys[(size_t)i * ICP_SUMS + lane] = icp_combine(sums, i, nb, lane);
-    else if (lane == ICP_SUMS) pairs[i] = icp_combine_n(cnts, i, nb);
-}
-
-// the defaults of an instance no system was accumulated for (iters == 0), and the running state
-__global__ __launch_bounds__(SIL_THREADS) void sil_init_kernel(int N, int* __restrict__ state, int* __restrict__ ok, int* __restrict__ iters_done,
-                                                                int* __restrict__ pairs, double* __restrict__ rms, int* __restrict__ sil_pairs,
-                                                                double* __restrict__ sil_rms) {
-    const int i = blockIdx.x * SIL_THREADS + threadIdx.x;
-    if (i >= N) return;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    state[(size_t)i * 2 + 0] = GDRN_ICP_RUNNING;
-    state[(size_t)i * 2 + 1] = 0;
-    ok[i] = 1;
-    iters_done[i] = 0;
-    pairs[i] = 0;
-    rms[i] = nan;
-    sil_pairs[i] = 0;
-    sil_rms[i] = nan;
+    icp_fold_band(acc, n_pairs, red, red_n, i, band, nb, sums, cnts);
 }
 
 // One wave per instance.  Prologue: the silhouette sums over their nb bands (nb = 1: a combined system as it is), then entry by entry
@@ -307,12 +262,12 @@ struct SilWs {
     unsigned char* flags;
 };
 long long sil_bytes(int N, int H, int W) {
-    const long long nb = sil_bands(H), px = (long long)N * H * W;
+    const long long nb = icp_bands(H), px = (long long)N * H * W;
     return (long long)N * (nb + 1) * ICP_SUMS * (long long)sizeof(double) + sil_pad8(gdrn_icp_workspace_bytes(N, H, W)) +
            (3 * px + (long long)N * (nb + 4)) * (long long)sizeof(int) + px;
 }
 SilWs sil_carve(void* workspace, int N, int H, int W) {
-    const size_t nb = sil_bands(H), px = (size_t)N * H * W;
+    const size_t nb = icp_bands(H), px = (size_t)N * H * W;
     SilWs w;
     char* p = reinterpret_cast<char*>(workspace);
     w.sums = reinterpret_cast<double*>(p);
@@ -347,7 +302,7 @@ int sil_launch_transform(const unsigned char* mask, const float* depth_scene, co
 
 int sil_launch_accumulate(const float* depth_ren, const float* depth_scene, const int* frame, int F, const double* K, const int* d2,
                           const int* nearest, int N, int H, int W, double sil_gate, double dist_gate, const SilWs& w, hipStream_t st) {
-    GDRN_LAUNCH(sil_accumulate_kernel, dim3(sil_bands(H), N), dim3(SIL_THREADS), 0, st, depth_ren, depth_scene, frame, F, K, d2, nearest, H, W,
+    GDRN_LAUNCH(sil_accumulate_kernel, dim3(icp_bands(H), N), dim3(ICP_THREADS), 0, st, depth_ren, depth_scene, frame, F, K, d2, nearest, H, W,
                 sil_gate * sil_gate, dist_gate, w.sums, w.cnts);
     GDRN_CHECK_LAUNCH();
     return GDRN_OK;
@@ -388,7 +343,7 @@ extern "C" int gdrn_sil_accumulate(const float* depth_ren, const float* depth_sc
     const SilWs w = sil_carve(workspace, N, H, W);
     const int bad = sil_launch_accumulate(depth_ren, depth_scene, frame, F, K, d2, nearest, N, H, W, sil_gate, dist_gate, w, st);
     if (bad != GDRN_OK) return bad;
-    GDRN_LAUNCH(sil_combine_kernel, dim3(N), dim3(64), 0, st, w.sums, w.cnts, sil_bands(H), sys, pairs);
+    GDRN_LAUNCH(icp_combine_kernel, dim3(N), dim3(64), 0, st, w.sums, w.cnts, icp_bands(H), sys, pairs);
     GDRN_CHECK_LAUNCH();
     return GDRN_OK;
 }
@@ -410,28 +365,27 @@ extern "C" int gdrn_icp_refine_sil(const double* verts, const int* faces, const 
                                    const unsigned char* mask_obs, int H, int W, double near, double far, int iters, double dist_gate,
                                    double normal_gate, int min_pairs, double sil_weight, double sil_gate, float* depth_ren_scratch, int* ok,
                                    int* iters_done, int* pairs, double* rms, int* sil_pairs, double* sil_rms, void* workspace, void* stream) {
-    if (!sil_frame_ok(N, H, W) || F < 0 || iters < 0 || min_pairs < 6 || !(dist_gate > 0.0) || !(normal_gate > 0.0)) return GDRN_ERR_ARG;
+    const RenderRows rows = {verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far};
+    const RenderScene scene = {depth_scene, frame, frame_host, F};
+    if (!sil_frame_ok(N, H, W) || iters < 0 || min_pairs < 6 || !(dist_gate > 0.0) || !(normal_gate > 0.0)) return GDRN_ERR_ARG;
     if (!sil_weight_ok(sil_weight) || !(sil_gate > 0.0)) return GDRN_ERR_ARG;
-    if (C <= 0 || f_max <= 0 || !(near > 0.0) || !(near < far)) return GDRN_ERR_ARG;
+    if (!loop_scalars_ok(rows, scene)) return GDRN_ERR_ARG;
     if (H > SIL_MAX_SIDE || W > SIL_MAX_SIDE) return GDRN_ERR_SHAPE;
     if (N == 0) return GDRN_OK;
-    if (!verts || !faces || !vert_off || !nverts || !face_off || !nfaces || !labels || !labels_host || !R || !t || !K || !depth_scene || !frame ||
-        !frame_host || !mask_obs || !depth_ren_scratch || !ok || !iters_done || !pairs || !rms || !sil_pairs || !sil_rms || !workspace ||
-        ((size_t)workspace & 7))
+    if (!mask_obs || !depth_ren_scratch || !ok || !iters_done || !pairs || !rms || !sil_pairs || !sil_rms || !workspace || ((size_t)workspace & 7))
         return GDRN_ERR_ARG;
-    if (N > 65535) return GDRN_ERR_SHAPE;
-    if (!host_in_range(labels_host, N, C) || !host_in_range(frame_host, N, F)) return GDRN_ERR_ARG;
+    int bad = loop_rows_check(rows, scene);
+    if (bad != GDRN_OK) return bad;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int nb = sil_bands(H);
+    const int nb = icp_bands(H);
     const SilWs w = sil_carve(workspace, N, H, W);
-    GDRN_LAUNCH(sil_init_kernel, dim3(cdiv(N, SIL_THREADS)), dim3(SIL_THREADS), 0, st, N, w.state, ok, iters_done, pairs, rms, sil_pairs, sil_rms);
+    GDRN_LAUNCH(icp_init_kernel, dim3(cdiv(N, ICP_THREADS)), dim3(ICP_THREADS), 0, st, N, w.state, ok, iters_done, pairs, rms, sil_pairs, sil_rms);
     GDRN_CHECK_LAUNCH();
     if (iters == 0) return GDRN_OK;
-    int bad = sil_launch_transform(mask_obs, depth_scene, frame, F, N, H, W, w.d2, w.nearest, w.contour, w, st);
+    bad = sil_launch_transform(mask_obs, depth_scene, frame, F, N, H, W, w.d2, w.nearest, w.contour, w, st);
     if (bad != GDRN_OK) return bad;
     for (int it = 0; it < iters; ++it) {
-        bad = gdrn_render_depth(verts, faces, vert_off, nverts, face_off, nfaces, C, f_max, labels, labels_host, R, t, K, N, H, W, near, far,
-                                depth_ren_scratch, stream);
+        bad = render_into(rows, depth_ren_scratch, stream);
         if (bad != GDRN_OK) return bad;
         bad = gdrn_icp_accumulate(depth_ren_scratch, depth_scene, frame, frame_host, F, K, N, H, W, dist_gate, normal_gate, w.sys_depth,
                                   w.pairs_depth, w.icp, stream);

@@ -48,11 +48,22 @@ def _gates(dist_gate, normal_gate):
     return dist_gate, normal_gate
 
 
-def normal_equations(depth_ren, depth_scene, frame, K, dist_gate=0.02, normal_gate=0.01):
-    """One accumulation on given renders: ``depth_ren`` [N,H,W] fp32 (the model under each estimate's pose, e.g. ``render.render_depth``'s),
-    ``depth_scene`` [F,H,W] fp32 (metres, 0 = no measurement), ``frame`` [N] (the frame of each estimate), ``K`` [N,3,3] or [3,3].  Returns a
-    dict of device tensors: A [N,6,6] fp64 (symmetric, full), b [N,6], sq [N] fp64 and pairs [N] int32."""
-    dist_gate, normal_gate = _gates(dist_gate, normal_gate)
+def _iters(iters, min_pairs, show=int):
+    """the rule of a loop's ``iters`` / ``min_pairs``, as ints; ``show``: how the error sentence prints the two"""
+    if int(iters) < 0 or int(min_pairs) < 6:
+        raise ValueError(f"iters {show(iters)} must be >= 0 and min_pairs {show(min_pairs)} >= 6 (the unknowns of a pose)")
+    return int(iters), int(min_pairs)
+
+
+def _call(fns, N, H, W, dev, args):
+    """``fns(lib)`` = (an entry point, its workspace query): the entry point on ``args(p)``, then a workspace of that size and the stream"""
+    entry, query = fns(cabi.load())
+    ws = devargs.workspace(query(N, H, W), dev, query.__name__[len("gdrn_"):])
+    cabi.check(entry(*args(cabi.ptr), cabi.ptr(ws), devargs.stream(dev)), entry.__name__[len("gdrn_"):])
+
+
+def _renders(depth_ren, depth_scene):
+    """renders against a scene: (depth_ren [N,H,W] fp32 contiguous, the scene of ``_scene``), on one device and alike in H, W"""
     if not isinstance(depth_ren, torch.Tensor) or depth_ren.device.type != "cuda":
         raise devargs.no_fallback("depth_ren", WHERE)
     if depth_ren.dtype != torch.float32 or depth_ren.dim() != 3:
@@ -63,24 +74,69 @@ def normal_equations(depth_ren, depth_scene, frame, K, dist_gate=0.02, normal_ga
         raise ValueError(f"depth_ren {tuple(ren.shape)} and depth_scene {tuple(scene.shape)} differ in H, W")
     if ren.device != scene.device:
         raise ValueError(f"depth_ren is on {ren.device}, depth_scene on {scene.device}")
+    return ren, scene
+
+
+def _accumulate(fns, depth_ren, depth_scene, frame, K, gates, mask_obs=None):
+    """One accumulate pass (``fns``: see ``_call``) on given renders -- with ``mask_obs`` its contour transform first, whose maps the silhouette
+    term's pass reads -- and the dict of ``normal_equations`` from the packed systems [N,28]: 21 of A's upper triangle row by row, 6 of b, sq"""
+    ren, scene = _renders(depth_ren, depth_scene)
     N, H, W = (int(s) for s in ren.shape)
-    dev = ren.device
+    dev, F = ren.device, int(scene.shape[0])
+    if mask_obs is not None:
+        _mask(mask_obs, scene, N)
     K = devargs.per_row_K(devargs.device_tensor(K, torch.float64, (-1, 3, 3), "K", WHERE), N)
-    F = int(scene.shape[0])
     fr, fr_host = devargs.index_vector(frame, N, F, dev, "frame")
+    maps = () if mask_obs is None else [contour_transform(mask_obs, scene, fr)[k] for k in ("d2", "nearest")]
     sys = torch.empty(max(N, 1), 28, dtype=torch.float64, device=dev)[:N]
     pairs = torch.empty(max(N, 1), dtype=torch.int32, device=dev)[:N]
     if N > 0:
-        lib = cabi.load()
-        ws = devargs.workspace(lib.gdrn_icp_workspace_bytes(N, H, W), dev, "icp_workspace_bytes")
-        p = cabi.ptr
-        cabi.check(lib.gdrn_icp_accumulate(p(ren), p(scene), p(fr), fr_host.ctypes.data, F, p(K), N, H, W, dist_gate, normal_gate, p(sys), p(pairs),
-                                           p(ws), devargs.stream(dev)), "icp_accumulate")
+        _call(fns, N, H, W, dev, lambda p: (p(ren), p(scene), p(fr), fr_host.ctypes.data, F, p(K), *(p(m) for m in maps), N, H, W, *gates, p(sys),
+                                            p(pairs)))
     iu = torch.triu_indices(6, 6, device=dev)
     A = torch.zeros(N, 6, 6, dtype=torch.float64, device=dev)
-    A[:, iu[0], iu[1]] = sys[:, :21]   # the packed upper triangle, row by row
+    A[:, iu[0], iu[1]] = sys[:, :21]
     A[:, iu[1], iu[0]] = sys[:, :21]
     return dict(A=A, b=sys[:, 21:27].contiguous(), sq=sys[:, 27].contiguous(), pairs=pairs)
+
+
+class _Loop:
+    """The preamble of a render loop (``icp_refine``, ``icp_refine_sil``, ``depth_align``): the checked tensors, the host index arrays, the
+    sizes and the device.  Nothing is loaded or launched here."""
+
+    def __init__(self, meshes, labels, R0, t0, K, depth_scene, frame, mask_obs=None):
+        self.meshes = meshes
+        self.R, self.t, self.K, self.N = devargs.poses(R0, t0, K, WHERE)
+        self.scene = _scene(depth_scene)
+        self.dev = self.R.device
+        if self.scene.device != self.dev:
+            raise ValueError(f"R0 is on {self.dev}, depth_scene on {self.scene.device}")
+        self.mask = () if mask_obs is None else (_mask(mask_obs, self.scene, self.N),)
+        self.F, self.H, self.W = (int(s) for s in self.scene.shape)
+        self.lab, self.lab_host = devargs.index_vector(labels, self.N, meshes.num_classes, self.dev, "labels")
+        self.fr, self.fr_host = devargs.index_vector(frame, self.N, self.F, self.dev, "frame")
+
+    def empty(self, dtype):
+        return torch.empty(self.N, dtype=dtype, device=self.dev)
+
+    def run(self, fns, R, t, near, far, scalars, outputs):
+        """The loop (``fns``: see ``_call``) on the poses ``R``, ``t`` (the caller's copies: in/out for the library): the 22 leading arguments
+        in ABI order -- the renderer's own list with the scene and the frames behind N, and the silhouette loop's mask behind F -- then the
+        loop's scalars, the scratch render, its outputs, the workspace and the stream"""
+        dev, N, H, W = self.dev, self.N, self.H, self.W
+        scratch = torch.empty(N, H, W, dtype=torch.float32, device=dev)
+        _call(fns, N, H, W, dev, lambda p: (
+            *self.meshes.lib_args(dev), p(self.lab), self.lab_host.ctypes.data, p(R), p(t), p(self.K), N, p(self.scene), p(self.fr),
+            self.fr_host.ctypes.data, self.F, *(p(m) for m in self.mask), H, W, float(near), float(far),
+            *scalars, p(scratch), *(p(o) for o in outputs)))
+
+
+def normal_equations(depth_ren, depth_scene, frame, K, dist_gate=0.02, normal_gate=0.01):
+    """One accumulation on given renders: ``depth_ren`` [N,H,W] fp32 (the model under each estimate's pose, e.g. ``render.render_depth``'s),
+    ``depth_scene`` [F,H,W] fp32 (metres, 0 = no measurement), ``frame`` [N] (the frame of each estimate), ``K`` [N,3,3] or [3,3].  Returns a
+    dict of device tensors: A [N,6,6] fp64 (symmetric, full), b [N,6], sq [N] fp64 and pairs [N] int32."""
+    gates = _gates(dist_gate, normal_gate)
+    return _accumulate(lambda lib: (lib.gdrn_icp_accumulate, lib.gdrn_icp_workspace_bytes), depth_ren, depth_scene, frame, K, gates)
 
 
 def icp_refine(meshes, labels, R0, t0, K, depth_scene, frame, iters=10, dist_gate=0.02, normal_gate=0.01, min_pairs=64, near=render.NEAR,
@@ -92,31 +148,13 @@ def icp_refine(meshes, labels, R0, t0, K, depth_scene, frame, iters=10, dist_gat
     degenerate -- fewer than ``min_pairs`` pairs or unobservable directions -- and keeps the pose it had); iters_done [N] int32 (steps applied);
     pairs [N] int32 and rms [N] fp64 (metres; NaN without a pair), those of the residual before the instance's last step."""
     dist_gate, normal_gate = _gates(dist_gate, normal_gate)
-    iters, min_pairs = int(iters), int(min_pairs)
-    if iters < 0 or min_pairs < 6:
-        raise ValueError(f"iters {iters} must be >= 0 and min_pairs {min_pairs} >= 6 (the unknowns of a pose)")
-    R, t, K, N = devargs.poses(R0, t0, K, WHERE)
-    scene = _scene(depth_scene)
-    dev = R.device
-    if scene.device != dev:
-        raise ValueError(f"R0 is on {dev}, depth_scene on {scene.device}")
-    F, H, W = (int(s) for s in scene.shape)
-    lab, lab_host = devargs.index_vector(labels, N, meshes.num_classes, dev, "labels")
-    fr, fr_host = devargs.index_vector(frame, N, F, dev, "frame")
-    R, t = R.clone(), t.clone()   # in/out for the library; the caller's tensors stay
-    out = dict(R=R, t=t, ok=torch.empty(N, dtype=torch.int32, device=dev), iters_done=torch.empty(N, dtype=torch.int32, device=dev),
-               pairs=torch.empty(N, dtype=torch.int32, device=dev), rms=torch.empty(N, dtype=torch.float64, device=dev))
-    if N == 0:
-        return out
-    lib = cabi.load()
-    tb = meshes.on(dev)
-    scratch = torch.empty(N, H, W, dtype=torch.float32, device=dev)
-    ws = devargs.workspace(lib.gdrn_icp_workspace_bytes(N, H, W), dev, "icp_workspace_bytes")
-    p = cabi.ptr
-    cabi.check(lib.gdrn_icp_refine(p(tb["verts"]), p(tb["faces"]), p(tb["vert_off"]), p(tb["nverts"]), p(tb["face_off"]), p(tb["nfaces"]),
-                                   meshes.num_classes, meshes.f_max, p(lab), lab_host.ctypes.data, p(R), p(t), p(K), N, p(scene), p(fr),
-                                   fr_host.ctypes.data, F, H, W, float(near), float(far), iters, dist_gate, normal_gate, min_pairs, p(scratch),
-                                   p(out["ok"]), p(out["iters_done"]), p(out["pairs"]), p(out["rms"]), p(ws), devargs.stream(dev)), "icp_refine")
+    iters, min_pairs = _iters(iters, min_pairs)
+    c = _Loop(meshes, labels, R0, t0, K, depth_scene, frame)
+    R, t = c.R.clone(), c.t.clone()   # in/out for the library; the caller's tensors stay
+    out = dict(R=R, t=t, ok=c.empty(torch.int32), iters_done=c.empty(torch.int32), pairs=c.empty(torch.int32), rms=c.empty(torch.float64))
+    if c.N > 0:
+        c.run(lambda lib: (lib.gdrn_icp_refine, lib.gdrn_icp_workspace_bytes), R, t, near, far, (iters, dist_gate, normal_gate, min_pairs),
+              (out["ok"], out["iters_done"], out["pairs"], out["rms"]))
     return out
 
 
@@ -178,36 +216,8 @@ def silhouette_equations(depth_ren, mask_obs, depth_scene, frame, K, sil_gate=8.
     A [N,6,6] fp64 (symmetric, full), b [N,6], sq [N] fp64 (metres squared) and pairs [N] int32 (pixels, two equations each)."""
     _, sil_gate = _sil_args(1.0, sil_gate)
     dist_gate, _ = _gates(dist_gate, 1.0)
-    if not isinstance(depth_ren, torch.Tensor) or depth_ren.device.type != "cuda":
-        raise devargs.no_fallback("depth_ren", WHERE)
-    if depth_ren.dtype != torch.float32 or depth_ren.dim() != 3:
-        raise ValueError("depth_ren must be an fp32 [N, H, W] tensor")
-    scene = _scene(depth_scene)
-    ren = devargs.device_tensor(depth_ren, None, None, "depth_ren", WHERE)
-    if ren.shape[1:] != scene.shape[1:]:
-        raise ValueError(f"depth_ren {tuple(ren.shape)} and depth_scene {tuple(scene.shape)} differ in H, W")
-    if ren.device != scene.device:
-        raise ValueError(f"depth_ren is on {ren.device}, depth_scene on {scene.device}")
-    N, H, W = (int(s) for s in ren.shape)
-    dev = ren.device
-    _mask(mask_obs, scene, N)
-    K = devargs.per_row_K(devargs.device_tensor(K, torch.float64, (-1, 3, 3), "K", WHERE), N)
-    F = int(scene.shape[0])
-    fr, fr_host = devargs.index_vector(frame, N, F, dev, "frame")
-    tr = contour_transform(mask_obs, scene, fr)
-    sys = torch.empty(max(N, 1), 28, dtype=torch.float64, device=dev)[:N]
-    pairs = torch.empty(max(N, 1), dtype=torch.int32, device=dev)[:N]
-    if N > 0:
-        lib = cabi.load()
-        ws = devargs.workspace(lib.gdrn_sil_workspace_bytes(N, H, W), dev, "sil_workspace_bytes")
-        p = cabi.ptr
-        cabi.check(lib.gdrn_sil_accumulate(p(ren), p(scene), p(fr), fr_host.ctypes.data, F, p(K), p(tr["d2"]), p(tr["nearest"]), N, H, W, sil_gate,
-                                           dist_gate, p(sys), p(pairs), p(ws), devargs.stream(dev)), "sil_accumulate")
-    iu = torch.triu_indices(6, 6, device=dev)
-    A = torch.zeros(N, 6, 6, dtype=torch.float64, device=dev)
-    A[:, iu[0], iu[1]] = sys[:, :21]   # the packed upper triangle, row by row
-    A[:, iu[1], iu[0]] = sys[:, :21]
-    return dict(A=A, b=sys[:, 21:27].contiguous(), sq=sys[:, 27].contiguous(), pairs=pairs)
+    return _accumulate(lambda lib: (lib.gdrn_sil_accumulate, lib.gdrn_sil_workspace_bytes), depth_ren, depth_scene, frame, K, (sil_gate, dist_gate),
+                       mask_obs)
 
 
 def icp_refine_sil(meshes, labels, R0, t0, K, depth_scene, frame, mask_obs, iters=20, sil_weight=1.0, sil_gate=8.0, dist_gate=0.02,
@@ -222,34 +232,15 @@ def icp_refine_sil(meshes, labels, R0, t0, K, depth_scene, frame, mask_obs, iter
     and rms are the depth term's) plus sil_pairs [N] int32 and sil_rms [N] fp64 (metres; NaN without a pair), the silhouette term's."""
     dist_gate, normal_gate = _gates(dist_gate, normal_gate)
     sil_weight, sil_gate = _sil_args(sil_weight, sil_gate)
-    iters, min_pairs = int(iters), int(min_pairs)
-    if iters < 0 or min_pairs < 6:
-        raise ValueError(f"iters {iters} must be >= 0 and min_pairs {min_pairs} >= 6 (the unknowns of a pose)")
-    R, t, K, N = devargs.poses(R0, t0, K, WHERE)
-    scene = _scene(depth_scene)
-    dev = R.device
-    if scene.device != dev:
-        raise ValueError(f"R0 is on {dev}, depth_scene on {scene.device}")
-    m = _mask(mask_obs, scene, N)
-    F, H, W = (int(s) for s in scene.shape)
-    lab, lab_host = devargs.index_vector(labels, N, meshes.num_classes, dev, "labels")
-    fr, fr_host = devargs.index_vector(frame, N, F, dev, "frame")
-    R, t = R.clone(), t.clone()   # in/out for the library; the caller's tensors stay
-    out = dict(R=R, t=t, ok=torch.empty(N, dtype=torch.int32, device=dev), iters_done=torch.empty(N, dtype=torch.int32, device=dev),
-               pairs=torch.empty(N, dtype=torch.int32, device=dev), rms=torch.empty(N, dtype=torch.float64, device=dev),
-               sil_pairs=torch.empty(N, dtype=torch.int32, device=dev), sil_rms=torch.empty(N, dtype=torch.float64, device=dev))
-    if N == 0:
-        return out
-    lib = cabi.load()
-    tb = meshes.on(dev)
-    scratch = torch.empty(N, H, W, dtype=torch.float32, device=dev)
-    ws = devargs.workspace(lib.gdrn_sil_workspace_bytes(N, H, W), dev, "sil_workspace_bytes")
-    p = cabi.ptr
-    cabi.check(lib.gdrn_icp_refine_sil(p(tb["verts"]), p(tb["faces"]), p(tb["vert_off"]), p(tb["nverts"]), p(tb["face_off"]), p(tb["nfaces"]),
-                                       meshes.num_classes, meshes.f_max, p(lab), lab_host.ctypes.data, p(R), p(t), p(K), N, p(scene), p(fr),
-                                       fr_host.ctypes.data, F, p(m), H, W, float(near), float(far), iters, dist_gate, normal_gate, min_pairs,
-                                       sil_weight, sil_gate, p(scratch), p(out["ok"]), p(out["iters_done"]), p(out["pairs"]), p(out["rms"]),
-                                       p(out["sil_pairs"]), p(out["sil_rms"]), p(ws), devargs.stream(dev)), "icp_refine_sil")
+    iters, min_pairs = _iters(iters, min_pairs)
+    c = _Loop(meshes, labels, R0, t0, K, depth_scene, frame, mask_obs)
+    R, t = c.R.clone(), c.t.clone()   # in/out for the library; the caller's tensors stay
+    out = dict(R=R, t=t, ok=c.empty(torch.int32), iters_done=c.empty(torch.int32), pairs=c.empty(torch.int32), rms=c.empty(torch.float64),
+               sil_pairs=c.empty(torch.int32), sil_rms=c.empty(torch.float64))
+    if c.N > 0:
+        c.run(lambda lib: (lib.gdrn_icp_refine_sil, lib.gdrn_sil_workspace_bytes), R, t, near, far,
+              (iters, dist_gate, normal_gate, min_pairs, sil_weight, sil_gate),
+              (out["ok"], out["iters_done"], out["pairs"], out["rms"], out["sil_pairs"], out["sil_rms"]))
     return out
 
 
@@ -268,16 +259,7 @@ def depth_offset(depth_ren, depth_scene, frame, gate=0.2, min_pairs=64):
     ``|depth_scene - depth_ren| <= gate``.  Returns a dict of device tensors: offset [N] fp64 (the exact median of ``depth_scene - depth_ren``
     over the pairs; NaN with fewer than ``min_pairs`` pairs), pairs, covered (pixels the render covers) and ok [N] int32."""
     gate, min_pairs, _ = _align_args(gate, min_pairs)
-    if not isinstance(depth_ren, torch.Tensor) or depth_ren.device.type != "cuda":
-        raise devargs.no_fallback("depth_ren", WHERE)
-    if depth_ren.dtype != torch.float32 or depth_ren.dim() != 3:
-        raise ValueError("depth_ren must be an fp32 [N, H, W] tensor")
-    scene = _scene(depth_scene)
-    ren = devargs.device_tensor(depth_ren, None, None, "depth_ren", WHERE)
-    if ren.shape[1:] != scene.shape[1:]:
-        raise ValueError(f"depth_ren {tuple(ren.shape)} and depth_scene {tuple(scene.shape)} differ in H, W")
-    if ren.device != scene.device:
-        raise ValueError(f"depth_ren is on {ren.device}, depth_scene on {scene.device}")
+    ren, scene = _renders(depth_ren, depth_scene)
     N, H, W = (int(s) for s in ren.shape)
     dev = ren.device
     F = int(scene.shape[0])
@@ -304,28 +286,12 @@ def depth_align(meshes, labels, R0, t0, K, depth_scene, frame, rounds=2, gate=0.
     translation it had and is left alone from then on); pairs, covered [N] int32 and offset [N] fp64 (NaN where ok is 0), those of the
     instance's last evaluated round.  Nothing is read back.  The caller's tensors stay."""
     gate, min_pairs, rounds = _align_args(gate, min_pairs, rounds)
-    R, t, K, N = devargs.poses(R0, t0, K, WHERE)
-    scene = _scene(depth_scene)
-    dev = R.device
-    if scene.device != dev:
-        raise ValueError(f"R0 is on {dev}, depth_scene on {scene.device}")
-    F, H, W = (int(s) for s in scene.shape)
-    lab, lab_host = devargs.index_vector(labels, N, meshes.num_classes, dev, "labels")
-    fr, fr_host = devargs.index_vector(frame, N, F, dev, "frame")
-    t = t.clone()   # in/out for the library; the caller's tensor stays
-    out = dict(t=t, ok=torch.empty(N, dtype=torch.int32, device=dev), pairs=torch.empty(N, dtype=torch.int32, device=dev),
-               covered=torch.empty(N, dtype=torch.int32, device=dev), offset=torch.empty(N, dtype=torch.float64, device=dev))
-    if N == 0:
-        return out
-    lib = cabi.load()
-    tb = meshes.on(dev)
-    scratch = torch.empty(N, H, W, dtype=torch.float32, device=dev)
-    ws = devargs.workspace(lib.gdrn_depth_align_workspace_bytes(N, H, W), dev, "depth_align_workspace_bytes")
-    p = cabi.ptr
-    cabi.check(lib.gdrn_depth_align(p(tb["verts"]), p(tb["faces"]), p(tb["vert_off"]), p(tb["nverts"]), p(tb["face_off"]), p(tb["nfaces"]),
-                                    meshes.num_classes, meshes.f_max, p(lab), lab_host.ctypes.data, p(R), p(t), p(K), N, p(scene), p(fr),
-                                    fr_host.ctypes.data, F, H, W, float(near), float(far), rounds, gate, min_pairs, p(scratch), p(out["ok"]),
-                                    p(out["pairs"]), p(out["covered"]), p(out["offset"]), p(ws), devargs.stream(dev)), "depth_align")
+    c = _Loop(meshes, labels, R0, t0, K, depth_scene, frame)
+    t = c.t.clone()   # in/out for the library; the caller's tensor stays
+    out = dict(t=t, ok=c.empty(torch.int32), pairs=c.empty(torch.int32), covered=c.empty(torch.int32), offset=c.empty(torch.float64))
+    if c.N > 0:
+        c.run(lambda lib: (lib.gdrn_depth_align, lib.gdrn_depth_align_workspace_bytes), c.R, t, near, far, (rounds, gate, min_pairs),
+              (out["ok"], out["pairs"], out["covered"], out["offset"]))
     return out
 
 
@@ -337,8 +303,7 @@ def refine_rgbd(meshes, labels, R0, t0, K, depth_scene, frame, rounds=2, gate=0.
     without it the call is what it was before the silhouette term existed.  Returns the second step's dict plus ``align``: the dict of
     ``depth_align``."""
     _gates(dist_gate, normal_gate)   # both steps' scalars are judged before either runs
-    if int(iters) < 0 or int(min_pairs) < 6:
-        raise ValueError(f"iters {iters} must be >= 0 and min_pairs {min_pairs} >= 6 (the unknowns of a pose)")
+    _iters(iters, min_pairs, show=lambda v: v)   # (the caller's values as given)
     if mask_obs is not None:
         _sil_args(sil_weight, sil_gate)
         _mask(mask_obs, _scene(depth_scene))

@@ -52,6 +52,11 @@ class MeshTable(devargs.DeviceTables):
         if device is not None:
             self.on(device)
 
+    def lib_args(self, device):
+        """the eight leading arguments of every library call that draws from the table: the six tables on ``device``, then C and f_max"""
+        tb, p = self.on(device), cabi.ptr
+        return (p(tb["verts"]), p(tb["faces"]), p(tb["vert_off"]), p(tb["nverts"]), p(tb["face_off"]), p(tb["nfaces"]), self.num_classes, self.f_max)
+
 
 def render_depth(table, labels, R, t, K, H, W, near=NEAR, far=FAR):
     """Depth [N,H,W] fp32 (camera-space z in metres, 0 where nothing is drawn) of N instances in one call: instance i is the mesh ``labels[i]`` of
@@ -60,13 +65,12 @@ def render_depth(table, labels, R, t, K, H, W, near=NEAR, far=FAR):
     R, t, K, N = devargs.poses(R, t, K, WHERE)
     dev = R.device
     lab, lab_host = devargs.index_vector(labels, N, table.num_classes, dev, "labels")
-    tb = table.on(dev)
+    mesh = table.lib_args(dev)
     H, W = int(H), int(W)
     depth = torch.empty(max(N, 0), max(H, 0), max(W, 0), dtype=torch.float32, device=dev)
     p = cabi.ptr
-    cabi.check(cabi.load().gdrn_render_depth(p(tb["verts"]), p(tb["faces"]), p(tb["vert_off"]), p(tb["nverts"]), p(tb["face_off"]), p(tb["nfaces"]),
-                                             table.num_classes, table.f_max, p(lab), lab_host.ctypes.data, p(R), p(t), p(K), N, H, W, float(near),
-                                             float(far), p(depth), devargs.stream(dev)), "render_depth")
+    cabi.check(cabi.load().gdrn_render_depth(*mesh, p(lab), lab_host.ctypes.data, p(R), p(t), p(K), N, H, W, float(near), float(far), p(depth),
+                                             devargs.stream(dev)), "render_depth")
     return depth
 
 

@@ -113,10 +113,9 @@ def render_visibility(table, labels, R, t, K, H, W, near=render.NEAR, far=render
     vis = torch.empty(max(N, 0), max(H, 0), max(W, 0), dtype=torch.int64, device=dev)
     if N == 0:
         return vis
-    tb, p = table.on(dev), cabi.ptr
-    cabi.check(cabi.load().gdrn_render_visibility(p(tb["verts"]), p(tb["faces"]), p(tb["vert_off"]), p(tb["nverts"]), p(tb["face_off"]),
-                                                  p(tb["nfaces"]), table.num_classes, table.f_max, p(lab), lab_host.ctypes.data, p(R), p(t), p(K),
-                                                  N, H, W, float(near), float(far), p(vis), devargs.stream(dev)), "render_visibility")
+    p = cabi.ptr
+    cabi.check(cabi.load().gdrn_render_visibility(*table.lib_args(dev), p(lab), lab_host.ctypes.data, p(R), p(t), p(K), N, H, W, float(near),
+                                                  float(far), p(vis), devargs.stream(dev)), "render_visibility")
     return vis
 
 
