@@ -316,13 +316,21 @@ _SIGS = {
     "gdrn_rigid_workspace_bytes": [I, I, I],
     "gdrn_rigid_ransac": [P, P, P, I, I, D, I, C.c_ulonglong, P, P, P, P, P, P, P, P],
     "gdrn_rigid_fit": [P, P, P, I, I, P, P, P, P, P],
+    "gdrn_verify_workspace_bytes": [I, I, I],
+    # renders, scene, frame (device, host), F | mask_obs, mask_index (device, host), M | N, H, W, tau | counts, sum_q, workspace, stream
+    "gdrn_verify_maps": [P, P, P, P, I, P, P, P, I, I, I, I, D, P, P, P, P],
+    "gdrn_verify_score": [P, P, I, I, D, D, I, P, P, P],
+    "gdrn_verify_select": [P, P, P, P, I, I, P, P, P],
+    # the mask group of gdrn_verify_maps, tau, penalty, min_covered | scratch, counts, sum_q, score, ok, workspace, stream
+    "gdrn_verify_poses": _LOOP + [P, P, P, I, D, D, I] + [P] * 7,
 }
 
 _SIGS["gdrn_half_format"] = []
 _RET_LL = ("gdrn_workspace_bytes", "gdrn_pose_metrics_workspace_bytes", "gdrn_pnp_workspace_bytes", "gdrn_vsd_workspace_bytes",
            "gdrn_mssd_mspd_workspace_bytes", "gdrn_model_prep_workspace_bytes", "gdrn_ad_errors_workspace_bytes",
            "gdrn_sym_errors_workspace_bytes", "gdrn_cou_maps_workspace_bytes", "gdrn_icp_workspace_bytes",
-           "gdrn_depth_align_workspace_bytes", "gdrn_sil_workspace_bytes", "gdrn_rigid_workspace_bytes")
+           "gdrn_depth_align_workspace_bytes", "gdrn_sil_workspace_bytes", "gdrn_rigid_workspace_bytes",
+           "gdrn_verify_workspace_bytes")
 EXPORTS = tuple(_SIGS.keys())
 _libs = {}
 

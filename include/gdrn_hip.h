@@ -1399,6 +1399,73 @@ int gdrn_rigid_ransac(const double* cam, const double* mod, const int* counts, i
 int gdrn_rigid_fit(const double* cam, const double* mod, const int* counts, int N, int stride, double* R, double* t, int* ok, double* rms,
                    void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Hypothesis verification behind the refinement above (added within ABI 5: new entry points, nothing changed): how well a candidate pose
+ * explains the observed depth frame and the observed instance mask, and which candidate of a detection explains them best.  gdrn_icp_refine's
+ * rms covers only the pairs that passed its own gates: a pose that pokes into measured free space, sits off the mask or hides behind a wall
+ * can come back with a small one.  The reference is RGB-only and has no counterpart; the entry points are pinned to geometry and to an
+ * integer / fp64 host restatement (tests/verify_host.py), bitwise.  The counts are integers and only integer atomics are used: the same call
+ * gives the same bits whatever the launch shape, and the candidates of a batch do not influence each other.
+ *
+ *   depth_ren, depth_scene, frame, frame_host, F: as for gdrn_icp_accumulate.  mask_obs [M][H][W] uint8 (nonzero = object) or NULL: no mask.
+ *   mask_index [N] int32 (device) / mask_index_host (the same values on the host, range-checked against M before any launch): the mask of
+ *   each candidate, so that the candidates of one detection share one mask;  both NULL: M must equal N and candidate i reads mask i.
+ *
+ * Per pixel p of candidate i, with zr = depth_ren[i][p], zc = depth_scene[frame[i]][p], m = mask_obs[mask_index[i]][p] != 0 (absent without a mask):
+ *   covered   zr > 0 (a NaN is not; +inf is).     usable   zc is finite and zc > 0.     e = (double)zr - (double)zc, exact.
+ *   a covered pixel is exactly one of
+ *     unknown    not usable                        no measurement
+ *     inlier     usable and fabs(e) <= tau         the render agrees with the observation
+ *     occluded   usable and e > tau                the observation is nearer: something stands in front
+ *     violated   usable and e < -tau               the observation is farther: the model claims a surface in measured free space
+ *   visible   covered and not occluded.
+ * counts [N][8] int32 = covered, inlier, occluded, violated, unknown, visible, mask_px (pixels with m set, covered or not), inter (pixels that
+ *   are visible and have m set);  without a mask mask_px = inter = 0.
+ * sum_q  [N] int64 = the sum over the inliers of (long long)floor(fabs(e) * 1048576.0): exact, a power-of-two scaling of an exact difference.
+ * score (one thread per candidate, fp64, contraction off, in this order):
+ *     tq    = tau * 1048576.0
+ *     fit   = (double)inlier - (double)sum_q / tq              truncated-linear: the sum over the inliers of (1 - |e| / tau), quantised
+ *     iou   = has_mask ? (uni > 0 ? (double)inter / (double)uni : 0.0) : 1.0,      uni = visible + mask_px - inter (int32)
+ *     score = (iou * fit - penalty * (double)violated) / (double)covered
+ *     ok    = covered >= min_covered;   ok == 0: score = -inf (nothing above is evaluated)
+ *   The score lies in [-penalty, 1].  The denominator is covered, not visible: a candidate hidden behind a surface has no evidence and must
+ *   not win.  The mask factor applies to the positive part only: a lower overlap never raises a score.
+ * select  per group g in [0, G): among the rows i with group[i] == g, ok[i] != 0 and score[i] == score[i] (not a NaN), the row with the
+ *   highest score, -0.0 ranking below +0.0;  ties go to the lowest row index.  best [G] int32 = that row, -1 without one;  best_score [G] fp64 =
+ *   its score, -inf without one.
+ *
+ * gdrn_verify_maps: counts and sum_q of N candidates on given renders.  One workgroup per (candidate, chunk of 2048 pixels): the render and
+ *   the mask are streamed over the whole frame, the observed depth is read only where the render is covered;  no alignment of the base
+ *   pointers, of H * W or of W is assumed.  workspace: gdrn_verify_workspace_bytes(N, H, W) bytes of device memory, 8-byte aligned;  the call
+ *   clears what it needs on the stream, the caller prepares nothing.
+ * gdrn_verify_score: score [N] fp64 and ok [N] int32 from counts and sum_q;  has_mask != 0: the counts were taken with a mask.
+ * gdrn_verify_select: group [N] int32 (device) / group_host (the same values on the host, range-checked against G before any launch).  Four
+ *   small launches: integer atomicMax of the scores' order-preserving 64-bit keys per group (in best_score's own memory), integer atomicMin of
+ *   the row index among the rows that hold the maximum.  No workspace.
+ * gdrn_verify_poses: the mesh table, labels, near and far exactly as gdrn_render_depth takes them, the leading arguments in the order of
+ *   gdrn_icp_refine;  R, t are only read.  On the one stream: gdrn_render_depth into depth_ren_scratch [N][H][W] fp32 (caller-owned), the
+ *   counting pass, the score.  Nothing is read back.  The same bits as the three calls one after the other.
+ * Status: GDRN_ERR_ARG for N < 0, H or W < 1, H * W of 2^31 - 1024 and more, F or G < 0, tau outside (0, 1] (so that every sum converts to
+ *   fp64 exactly), a penalty that is not finite and >= 0, min_covered < 1, a frame, a label, a group or a mask index out of range, a mask with
+ *   M < 1, with one copy of its index but not the other, or without an index and M != N, the rasterizer's argument rules, or (N > 0, resp.
+ *   G > 0) a NULL pointer or a misaligned workspace;  GDRN_ERR_SHAPE for N > 65535 in gdrn_verify_maps and gdrn_verify_poses, and the
+ *   rasterizer's shape rules.  Everything is checked on the host before a stream or a device pointer is touched;  N == 0 launches nothing
+ *   (gdrn_verify_select with N == 0 and G > 0 writes -1 and -inf). */
+long long gdrn_verify_workspace_bytes(int N, int H, int W);
+int gdrn_verify_maps(const float* depth_ren, const float* depth_scene, const int* frame, const int* frame_host, int F,
+                     const unsigned char* mask_obs, const int* mask_index, const int* mask_index_host, int M, int N, int H, int W, double tau,
+                     int* counts, long long* sum_q, void* workspace, void* stream);
+int gdrn_verify_score(const int* counts, const long long* sum_q, int N, int has_mask, double tau, double penalty, int min_covered,
+                      double* score, int* ok, void* stream);
+int gdrn_verify_select(const double* score, const int* ok, const int* group, const int* group_host, int N, int G, int* best,
+                       double* best_score, void* stream);
+int gdrn_verify_poses(const double* verts, const int* faces, const int* vert_off, const int* nverts, const int* face_off, const int* nfaces, int C,
+                      int f_max, const int* labels, const int* labels_host, const double* R, const double* t, const double* K, int N,
+                      const float* depth_scene, const int* frame, const int* frame_host, int F, int H, int W, double near, double far,
+                      const unsigned char* mask_obs, const int* mask_index, const int* mask_index_host, int M, double tau, double penalty,
+                      int min_covered, float* depth_ren_scratch, int* counts, long long* sum_q, double* score, int* ok, void* workspace,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
