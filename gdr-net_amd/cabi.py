@@ -323,6 +323,11 @@ _SIGS = {
     "gdrn_verify_select": [P, P, P, P, I, I, P, P, P],
     # the mask group of gdrn_verify_maps, tau, penalty, min_covered | scratch, counts, sum_q, score, ok, workspace, stream
     "gdrn_verify_poses": _LOOP + [P, P, P, I, D, D, I] + [P] * 7,
+    "gdrn_roi_components": [P, I, I, F, P, P, P, P],
+    # map, geom (device, host) | B, res, H, W, thr | mask, area, bbox, stream
+    "gdrn_roi_paste_masks": [P, P, P, I, I, I, I, F, P, P, P, P],
+    # map, geom (device, host), frame_host, csr (device, host) | B, F, res, H, W, thr | index, mask, area, bbox, stream
+    "gdrn_roi_paste_exclusive": [P, P, P, P, P, P, I, I, I, I, I, F, P, P, P, P, P],
 }
 
 _SIGS["gdrn_half_format"] = []

@@ -1466,6 +1466,61 @@ int gdrn_verify_poses(const double* verts, const int* faces, const int* vert_off
                       int min_covered, float* depth_ren_scratch, int* counts, long long* sum_q, double* score, int* ok, void* workspace,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Predicted instance masks in the frame (added within ABI 5: new entry points, nothing changed): the link between the mask head's output --
+ * gdrn_correspondences ends at a [res][res] probability map in crop coordinates -- and the steps above that take an observed mask in frame
+ * coordinates (gdrn_icp_refine_sil, gdrn_verify_maps / _poses, gdrn_cou_maps, gdrn_rle_count).  The reference has no counterpart on the path
+ * (its custom evaluator imports another package's paste with another box convention); the entry points are pinned to the arithmetic stated
+ * here, to a numpy fp64 restatement (tests/paste_host.py) bitwise, and through it to independent implementations.  Only integer atomics are
+ * used: the same call gives the same bits, and the rows of a batch (in the exclusive form: the frames) do not influence each other.
+ *
+ * gdrn_roi_components: the largest blob of each map.  prob [B][res][res] fp32, 2 <= res <= 64.  A pixel is foreground iff prob > thr (the
+ *   strict fp32 comparison of gdrn_correspondences), a non-finite value counting as 0.  Components are 8-connected.  The kept component is the
+ *   one with the most pixels; among equals the one that holds the lowest row-major pixel index.
+ *     filtered [B][res][res] fp32 = prob where the pixel belongs to the kept component, 0 elsewhere
+ *     num_comp [B] int32 = the number of components;  kept_px [B] int32 = the pixels of the kept one (0 for a map without foreground)
+ *   One workgroup per map, the labels in LDS: minimum-label propagation with pointer jumping, at most res^2 rounds (an explicit bound: a round
+ *   that changes anything retires a root for good, and there are at most res^2 roots).
+ *
+ * gdrn_roi_paste_masks: B maps into B masks of H x W.  map [B][res][res] fp32;  geom [B][3] fp64 (device) = cx, cy, scale of each row, the
+ *   crop's centre in frame pixels and its side;  geom_host: the same values on the host, checked before any launch.  For frame pixel (x, y) of
+ *   row n, in fp64 and in this order (contraction off):
+ *     k = (double)res / scale
+ *     u = ((double)x - cx) * k + 0.5 * res          v = ((double)y - cy) * k + 0.5 * res
+ *     the pixel is 0, and nothing is read, unless -1 < u < res and -1 < v < res
+ *     u0 = floor(u), fu = u - u0                    v0 = floor(v), fv = v - v0
+ *     m00 = map[v0][u0], m01 = map[v0][u0 + 1], m10 = map[v0 + 1][u0], m11 = map[v0 + 1][u0 + 1], widened to fp64;  a tap outside the map,
+ *       or a non-finite one, is 0
+ *     a = m00 * (1 - fu) + m01 * fu                 b = m10 * (1 - fu) + m11 * fu                 p = a * (1 - fv) + b * fv
+ *     mask[n][y][x] = p > (double)thr
+ *   This is bilinear sampling of the map with a zero border at the exact inverse of the ideal crop map of get_affine_transform(center, scale,
+ *   0, res): crop index res / 2 lies on (cx, cy), integer coordinates are pixel centres.  It is NOT the inverse of the 1 / 1024 fixed-point
+ *   walk gdrn_roi_crop_inputs follows for the forward crop (cv2.warpAffine's), which rounds a source position to 1 / 1024 pixel and an interpolation weight to 1 / 32.
+ *     mask [B][H][W] uint8, 0 / 1, every byte written
+ *     area [B] int32, bbox [B][4] int32 = x1, y1, x2, y2 of the set pixels, bottom-right inclusive;  an empty mask: area 0 and 0, 0, W - 1,
+ *       H - 1 -- gdrn_rle_count's convention exactly
+ *   Three launches (two of them one thread per row: the clearing and the empty-mask rule of area / bbox).  A lane writes 16-byte vectors where
+ *   the mask's first byte is 16-byte aligned, single bytes otherwise.
+ *
+ * gdrn_roi_paste_exclusive: the same paste, each frame pixel given to at most one row.  frame_host [B] int32: the frame of each row, within
+ *   [0, F);  csr [F + 1 + B] int32 (device) / csr_host (the same values on the host): the offsets of the frames followed by the rows of frame
+ *   0, of frame 1, ..., each frame's in ascending order -- the call refuses a csr_host that is not exactly that list of frame_host.  Among the
+ *   rows of a pixel's frame with p > (double)thr there, the greatest p wins, compared in fp64;  equal p goes to the lowest row.
+ *     index [F][H][W] int32 = the winning row, -1 without one
+ *     mask [B][H][W] uint8 = 1 where the row won, every byte written;  area, bbox: of these masks, as above
+ *   A gather: one lane per 16 frame pixels walks the rows of its frame.  No atomics on values, no workspace.
+ *
+ * Status: GDRN_ERR_ARG for B < 0, res outside [2, 64], H or W < 1, B * H * W or F * H * W (gdrn_roi_components: B * res * res) of 2^31 and
+ *   more, a thr that is not finite and >= 0, a scale that is not finite and > 0, a centre that is not finite, a frame outside [0, F), a
+ *   csr_host that does not match frame_host, or (B > 0) a NULL pointer.  Everything is checked on the host before a stream or a device
+ *   pointer is touched;  B == 0 succeeds and writes nothing. */
+int gdrn_roi_components(const float* prob, int B, int res, float thr, float* filtered, int* num_comp, int* kept_px, void* stream);
+int gdrn_roi_paste_masks(const float* map, const double* geom, const double* geom_host, int B, int res, int H, int W, float thr,
+                         unsigned char* mask, int* area, int* bbox, void* stream);
+int gdrn_roi_paste_exclusive(const float* map, const double* geom, const double* geom_host, const int* frame_host, const int* csr,
+                             const int* csr_host, int B, int F, int res, int H, int W, float thr, int* index, unsigned char* mask, int* area,
+                             int* bbox, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
