@@ -27,6 +27,7 @@ import torch.nn as nn
 
 from . import cabi
 from .engine import LOSS_NAMES, Engine
+from .switches import read
 
 logger = logging.getLogger(__name__)
 
@@ -34,26 +35,6 @@ try:  # the reference pushes vis/* scalars into detectron2's EventStorage from i
     from detectron2.utils.events import get_event_storage as _d2_get_event_storage
 except Exception:  # detectron2 is not a dependency of this package
     _d2_get_event_storage = None
-
-
-class _ScalarSink:
-    def __init__(self):
-        self.scalars = {}
-
-    def put_scalars(self, **kw):
-        self.scalars.update(kw)
-
-
-_fallback_storage = _ScalarSink()
-
-
-def get_event_storage():
-    if _d2_get_event_storage is not None:
-        try:
-            return _d2_get_event_storage()
-        except Exception:
-            pass
-    return _fallback_storage
 
 
 # resnet_backbone.py:8-14 (only BasicBlock depths are on the path)
@@ -235,29 +216,66 @@ class _PathFn(torch.autograd.Function):
             # the plan keeps ONE set of activations per (batch size, mode): a second forward overwrote what this backward needs
             raise cabi.GdrnHipError("backward of a forward pass whose activations were overwritten by a later forward of the same "
                                     "batch size: call loss.backward() before the next model(...) call")
-        dyn = e.loss_scale_dev() if hasattr(e, "loss_scale_dev") else None   # fp16 with the dynamic loss scale: the device-resident state (None otherwise)
-        ls = 1.0 if dyn is not None else float(getattr(e, "_ls_host", getattr(e, "loss_scale", 1.0)))
-        if dyn is not None:
-            gl = glosses.to(torch.float32).contiguous()
-            cabi.check(e.lib.gdrn_scaled_loss_weights(gl.data_ptr(), None, 8, dyn.ptr, plan.gw.data_ptr(), e._stream()), "scaled_loss_weights")
-        else:
-            plan.gw.copy_(glosses.to(torch.float32) * ls)   # (fp16, static: the engine's loss scale on the whole gradient chain)
-        plan._gw_key = None
+        dyn = e.loss_scale_dev()   # fp16 with the dynamic loss scale: the device-resident state (None otherwise)
+        ls = 1.0 if dyn is not None else e._ls_host   # (fp16, static: the engine's loss scale on the whole gradient chain)
+        _seed_loss_gradient(plan, e, (glosses.to(torch.float32).contiguous(), None), dyn, ls, cacheable=False)
         plan.run_backward(ctx.kctx, on_bucket=ctx.model._on_bucket)
         red = getattr(ctx.model, "_reducer", None)
         if red is not None:
             # autograd clones these views into .grad on the compute stream right after we return: the bucket all-reduces
             # running on the reducer's side stream must have landed (and the mean be applied) before that
             red.finish()
-        if dyn is not None:
-            ctx.model._unscale_for_external_optimizer(e, dyn, 1.0)
-        elif ls != 1.0:
-            e.grad_flat.mul_(1.0 / ls)   # .grad is the unscaled gradient, as after GradScaler.unscale_()
+        _hand_out_gradients(e, dyn, 1.0 / ls)   # .grad is the unscaled gradient, as after GradScaler.unscale_()
         return (None, None, None) + tuple(e.grads[n] for n in e.param_names)
+
+
+def _seed_loss_gradient(plan, eng, weights, dyn, ls, cacheable):
+    """dL/dloss_k = w_k [x w2_k] x the loss scale into plan.gw, the one place that writes it.  weights: (w, w2 or None), w contiguous fp32 on the device."""
+    # Under a dynamic scale `dyn` the product is formed by a device launch with the scale as the DEVICE holds it (it changes without the host
+    # knowing); otherwise on the host with the static scale `ls` and copied in -- once, not every step, when `cacheable` (the config's own
+    # weights, keyed by plan._gw_key on the tensor's address and version); every other write resets the key
+    w, w2 = weights
+    key = (w.data_ptr(), w._version, ls) if cacheable and dyn is None else None
+    if dyn is not None:
+        w2 = None if w2 is None else torch.as_tensor(w2, dtype=torch.float32, device=eng.dev).contiguous()
+        cabi.check(eng.lib.gdrn_scaled_loss_weights(w.data_ptr(), None if w2 is None else w2.data_ptr(), 8, dyn.ptr, plan.gw.data_ptr(), eng._stream()),
+                   "scaled_loss_weights")
+    elif key is None or getattr(plan, "_gw_key", None) != key:
+        plan.gw.copy_(w * ls if w2 is None else w * w2 * ls)
+    plan._gw_key = key
+
+
+def _hand_out_gradients(eng, dyn, factor):
+    """the one seam for gradients LEAVING the engine (autograd's .grad, train_step(optimizer=None), an optimizer that takes no grad_scale)"""
+    # g <- g * factor; under a dynamic loss scale the finite check, the division by the device's scale (or zeros) and the scale's bookkeeping with it
+    if dyn is not None:
+        GDRN._unscale_for_external_optimizer(eng, dyn, factor)
+    elif factor != 1.0:
+        eng.grad_flat.mul_(factor)
+
+
+def _update_schedule(optimizer, reducer, on_bucket, eng, dyn):
+    """when the optimizer update of GDRN.train_step runs: "per_bucket" | "guarded" | "whole" (GDRN._step_*)"""
+    # per_bucket: the update of a gradient bucket goes out as soon as the bucket is final, under the rest of the backward pass (Ranger.step_buckets_*),
+    # instead of behind the whole pass: on one GPU on the engine's side stream right behind the bucket's weight-gradient reduction; with a GradReducer
+    # attached (dist.attach) on the reducer's stream right behind the bucket's all-reduce, with the 1/world factor folded into the update.
+    # guarded: fp16 with the dynamic loss scale -- the update waits for the finite check over ALL gradients (a bucket applied under the backward pass
+    # could not be taken back when a later bucket overflows, ADVICE r4)
+    if dyn is not None:
+        return "guarded"
+    mine = reducer is not None and on_bucket == reducer.on_bucket and reducer.defer_scale and (reducer.cuda or not reducer.active)
+    early = (optimizer is not None and (mine or (reducer is None and on_bucket is None)) and eng.wgrad_stream
+             and hasattr(optimizer, "step_buckets_begin") and read("GDRN_EARLY_OPT"))
+    return "per_bucket" if early else "whole"
 
 
 class _StagingShapeChanged(Exception):
     pass
+
+
+# the arguments of GDRN.forward that GDRN._prepare stages (the other ones are accepted for the reference's call and not used)
+_PREPARE_ARGS = ("gt_xyz", "gt_mask_trunc", "gt_mask_visib", "gt_region", "gt_ego_rot", "gt_points", "sym_infos", "gt_trans", "gt_trans_ratio",
+                 "roi_coord_2d", "roi_cams", "roi_centers", "roi_whs", "roi_extents", "resize_ratios")
 
 
 class GDRN(nn.Module):
@@ -279,7 +297,7 @@ class GDRN(nn.Module):
         # gradients out -- train_step with or without an optimizer, loss.backward() -- runs the finite check, and an overflowed pass leaves zero
         # gradients / a skipped fused step, never inf / NaN); cfg.TEST.AMP_TEST (autocast around the test-time forward, gdrn_evaluator.py:568)
         # -> fp16 inference (eval-mode forward) whatever the training arithmetic is.
-        explicit = cfg.MODEL.CDPN.get("HIP_DTYPE", os.environ.get("GDRN_HIP_DTYPE"))
+        explicit = cfg.MODEL.CDPN.get("HIP_DTYPE", read("GDRN_HIP_DTYPE"))
         solver, test = cfg.get("SOLVER", None), cfg.get("TEST", None)
         amp_train = bool(solver is not None and solver.get("AMP", None) is not None and solver.AMP.get("ENABLED", False))
         amp_test = bool(test is not None and test.get("AMP_TEST", False))
@@ -486,33 +504,18 @@ class GDRN(nn.Module):
         optimizer.step()`` (core/gdrn_modeling/engine.py:244-280).  Returns the [8] tensor of weighted losses (device,
         order engine.LOSS_NAMES; the values of forward()'s loss_dict)."""
         assert self.training, "train_step needs model.train()"
-        a = dict(gt_xyz=None, gt_mask_trunc=None, gt_mask_visib=None, gt_region=None, gt_ego_rot=None, gt_points=None, sym_infos=None,
-                 gt_trans=None, gt_trans_ratio=None, roi_coord_2d=None, roi_cams=None, roi_centers=None, roi_whs=None, roi_extents=None,
-                 resize_ratios=None)
-        a.update({k: v for k, v in kw.items() if k in a})
-        if loss_weights is None and self._on_bucket is None and os.environ.get("GDRN_GRAPH", "0") == "1":
+        a = {k: kw.get(k) for k in _PREPARE_ARGS}
+        if loss_weights is None and self._on_bucket is None and read("GDRN_GRAPH"):
             out = self._train_step_graph(x, optimizer, a)
             if out is not None:
                 return out
         eng, plan, kctx = self._prepare(x, True, a)
-        eng = plan.e
         # (r6) dL/dloss_k is known BEFORE the forward pass here (unlike under autograd): written first, so that the pose kernel can leave dL/dfc
         # itself (no combine / cast launches in front of the backward pass) and the loss-finalize launch the weighted loss vector this returns
         seam = eng.fc_tail and eng.h16 and bool(plan.acc_rows)
         dyn = eng.loss_scale_dev()   # fp16, dynamic loss scale: its state on the device (None: bf16 / fp32 / fp16 with a static scale)
         ls = 1.0 if dyn is not None else eng._ls_host   # static loss scale on dL/dloss, divided out where the optimizer reads the gradients
-        if dyn is not None:
-            # dL/dloss_k = weight_k x the scale as the DEVICE holds it (it changes without the host knowing): one 8-thread launch per step
-            lw2 = None if loss_weights is None else torch.as_tensor(loss_weights, dtype=torch.float32, device=eng.dev).contiguous()
-            cabi.check(eng.lib.gdrn_scaled_loss_weights(self._loss_w.data_ptr(), None if lw2 is None else lw2.data_ptr(), 8, dyn.ptr, plan.gw.data_ptr(),
-                                                        eng._stream()), "scaled_loss_weights")
-            plan._gw_key = None
-        elif loss_weights is not None:
-            plan.gw.copy_(self._loss_w * loss_weights * ls)
-            plan._gw_key = None
-        elif getattr(plan, "_gw_key", None) != (self._loss_w.data_ptr(), self._loss_w._version, ls):
-            plan.gw.copy_(self._loss_w * ls)  # dL/dloss_k = the config's loss weights: written once, not every step
-            plan._gw_key = (self._loss_w.data_ptr(), self._loss_w._version, ls)
+        _seed_loss_gradient(plan, eng, (self._loss_w, loss_weights), dyn, ls, cacheable=loss_weights is None)
         if seam:
             out = torch.empty(8, dtype=torch.float32, device=eng.dev)   # this call's own: the kernel reads the pointer at launch
             kctx["seeded"], kctx["loss_w"], kctx["weighted"] = True, self._loss_w.data_ptr(), out.data_ptr()
@@ -522,83 +525,79 @@ class GDRN(nn.Module):
             # ends ~0.1 ms before the side stream does: behind the final join the one small launch and its gap were the step's last 15 us
             out = plan.losses * self._loss_w
         red = getattr(self, "_reducer", None)
-        # The optimizer update of a gradient bucket goes out as soon as the bucket is final, under the rest of the backward pass
-        # (Ranger.step_buckets_*), instead of behind the whole pass: on one GPU on the engine's side stream right behind the bucket's
-        # weight-gradient reduction; with a GradReducer attached (dist.attach) on the reducer's stream right behind the bucket's all-reduce,
-        # with the 1/world factor folded into the update.  The bucket's operand copies for the next step follow on the same stream.
-        mine = red is not None and self._on_bucket == red.on_bucket and red.defer_scale and (red.cuda or not red.active)
-        # (fp16 with the dynamic loss scale: the update waits for the finite check over ALL gradients -- a bucket applied under the backward
-        #  pass could not be taken back when a later bucket overflows)
-        guard = dyn is not None
-        early = (optimizer is not None and (mine or (red is None and self._on_bucket is None)) and eng.wgrad_stream and not guard
-                 and hasattr(optimizer, "step_buckets_begin") and os.environ.get("GDRN_EARLY_OPT", "1") != "0")
-        if early:
-            if getattr(eng, "_bucket_of", None) is None or getattr(eng, "_bucket_of_bounds", None) != tuple(eng.bucket_bounds):
-                off = {id(eng.P[n]): eng.grad_offsets[n] for n in eng.param_names}
-                eng._bucket_of = lambda p_, off=off, bb=eng.bucket_bounds: next(i for i, (lo, hi) in enumerate(bb) if lo <= off[id(p_)] < hi)
-                eng._bucket_of_bounds = tuple(eng.bucket_bounds)
-            early = optimizer.step_buckets_begin({eng.P[n]: eng.grads[n] for n in eng.param_names}, eng._bucket_of, len(eng.bucket_bounds),
-                                                 grad_scale=(red.grad_scale if red is not None else 1.0) / ls)
-        if early:
-            packed = []
-
-            def bucket_done(b):   # called on the side stream behind the bucket's weight-gradient reduction
-                if red is not None and red.active:
-                    red.on_bucket(b)                       # all-reduce on the reducer's stream behind an event of this stream
-                    with torch.cuda.stream(red.stream):    # ... and behind it, in stream order, the update + the operand copies
-                        optimizer.step_bucket(b)
-                        packed.append(eng.repack_bucket(b))
-                    return
-                optimizer.step_bucket(b)
-                packed.append(eng.repack_bucket(b))
-
-            try:
-                plan.run_backward(kctx, on_bucket=bucket_done)
-            except BaseException:
-                optimizer.step_buckets_abort()   # step counters untouched
-                raise
-            if red is not None:
-                red.wait()   # the main stream (next forward, the caller) behind every bucket's exchange + update
-            optimizer.step_buckets_end()
-            if red is not None and red.active and red.world > 1:
-                self._dp_divergence_check(eng)
-            if packed and all(packed):
-                eng.mark_packed()
-            return out
-        plan.run_backward(kctx, on_bucket=self._on_bucket)
-        gs = 1.0 / ls
-        if red is not None:
-            red.wait()
-            gs = red.grad_scale / ls  # 1/world, folded into the fused optimizer's gradient read
-        if guard:
-            # fp16 with the dynamic loss scale, decided on the device (r6): finite check over the flat gradient buffer (behind the all-reduce: every
-            # rank decides alike) -> fused Ranger that is a no-op when the flag is up, divides by the scale and counts applied steps itself ->
-            # GradScaler.update's bookkeeping as a one-thread launch.  No host read: the host keeps launching (r5 read the flag every step).
-            eng = plan.e
-            cabi.check(eng.lib.gdrn_nonfinite_flag(eng.grad_flat.data_ptr(), eng.grad_flat.numel(), dyn.ptr, eng._stream()), "nonfinite_flag")
-            grads = {eng.P[n]: eng.grads[n] for n in eng.param_names}
-            if optimizer is not None and hasattr(optimizer, "step_dyn") and optimizer.step_dyn(grads, gs, dyn):
-                cabi.check(eng.lib.gdrn_loss_scale_update(dyn.ptr, 1, eng._stream()), "loss_scale_update")
-                return out
-            # gradients for an optimizer that is not the fused Ranger (or none): unscaled, zeroed if the step overflowed; such an optimizer's
-            # step is skipped on the host's reading of the state (GradScaler.step does the same read)
-            self._unscale_for_external_optimizer(eng, dyn, gs)
-            if optimizer is not None and not dyn.read()["last_overflowed"]:
-                optimizer.step(grads=grads) if getattr(optimizer, "takes_grad_scale", False) else self._step_foreign(optimizer, grads)
-            return out
-        if optimizer is not None:
-            eng = plan.e
-            grads = {eng.P[n]: eng.grads[n] for n in eng.param_names}
-            if gs != 1.0 and not getattr(optimizer, "takes_grad_scale", False):
-                eng.grad_flat.mul_(gs)
-                gs = 1.0
-            if gs != 1.0:
-                optimizer.step(grads=grads, grad_scale=gs)
-            else:
-                optimizer.step(grads=grads)
-        elif gs != 1.0:
-            plan.e.grad_flat.mul_(gs)
+        schedule = _update_schedule(optimizer, red, self._on_bucket, eng, dyn)
+        if not (schedule == "per_bucket" and self._step_per_bucket(plan, kctx, eng, optimizer, red, ls)):   # (False: that path does not apply)
+            (self._step_guarded if schedule == "guarded" else self._step_whole)(plan, kctx, eng, optimizer, red, ls, dyn)
         return out
+
+    def _step_per_bucket(self, plan, kctx, eng, optimizer, red, ls):
+        """backward pass with every bucket's update and its operand copies for the next step behind the bucket; False: nothing was launched"""
+        if getattr(eng, "_bucket_of", None) is None or getattr(eng, "_bucket_of_bounds", None) != tuple(eng.bucket_bounds):
+            off = {id(eng.P[n]): eng.grad_offsets[n] for n in eng.param_names}
+            eng._bucket_of = lambda p_, off=off, bb=eng.bucket_bounds: next(i for i, (lo, hi) in enumerate(bb) if lo <= off[id(p_)] < hi)
+            eng._bucket_of_bounds = tuple(eng.bucket_bounds)
+        if not optimizer.step_buckets_begin(eng.grad_map(), eng._bucket_of, len(eng.bucket_bounds),
+                                            grad_scale=(red.grad_scale if red is not None else 1.0) / ls):
+            return False
+        packed = []
+
+        def bucket_done(b):   # called on the side stream behind the bucket's weight-gradient reduction
+            if red is not None and red.active:
+                red.on_bucket(b)                       # all-reduce on the reducer's stream behind an event of this stream
+                with torch.cuda.stream(red.stream):    # ... and behind it, in stream order, the update + the operand copies
+                    optimizer.step_bucket(b)
+                    packed.append(eng.repack_bucket(b))
+                return
+            optimizer.step_bucket(b)
+            packed.append(eng.repack_bucket(b))
+
+        try:
+            plan.run_backward(kctx, on_bucket=bucket_done)
+        except BaseException:
+            optimizer.step_buckets_abort()   # step counters untouched (ADVICE r3)
+            raise
+        if red is not None:
+            red.wait()   # the main stream (next forward, the caller) behind every bucket's exchange + update
+        optimizer.step_buckets_end()
+        if red is not None and red.active and red.world > 1:
+            self._dp_divergence_check(eng)
+        if packed and all(packed):
+            eng.mark_packed()
+        return True
+
+    def _backward_whole(self, plan, kctx, red, ls):
+        """the backward pass with no update under it; returns the factor its gradients are still to be multiplied by"""
+        plan.run_backward(kctx, on_bucket=self._on_bucket)
+        if red is None:
+            return 1.0 / ls
+        red.wait()
+        return red.grad_scale / ls  # 1/world, folded into the fused optimizer's gradient read
+
+    def _step_guarded(self, plan, kctx, eng, optimizer, red, ls, dyn):
+        """the update behind the whole backward pass and behind the device's decision on it (fp16, dynamic loss scale)"""
+        # decided on the device (r6): finite check over the flat gradient buffer (behind the all-reduce: every rank decides alike) -> fused Ranger
+        # that is a no-op when the flag is up, divides by the scale and counts applied steps itself -> GradScaler.update's bookkeeping as a
+        # one-thread launch.  No host read: the host keeps launching (r5 read the flag every step)
+        gs = self._backward_whole(plan, kctx, red, ls)
+        cabi.check(eng.lib.gdrn_nonfinite_flag(eng.grad_flat.data_ptr(), eng.grad_flat.numel(), dyn.ptr, eng._stream()), "nonfinite_flag")
+        grads = eng.grad_map()
+        if optimizer is not None and hasattr(optimizer, "step_dyn") and optimizer.step_dyn(grads, gs, dyn):
+            cabi.check(eng.lib.gdrn_loss_scale_update(dyn.ptr, 1, eng._stream()), "loss_scale_update")
+            return
+        # gradients for an optimizer that is not the fused Ranger (or none): unscaled, zeroed if the step overflowed; such an optimizer's
+        # step is skipped on the host's reading of the state (GradScaler.step does the same read)
+        _hand_out_gradients(eng, dyn, gs)
+        if optimizer is not None and not dyn.read()["last_overflowed"]:
+            optimizer.step(grads=grads) if getattr(optimizer, "takes_grad_scale", False) else self._step_foreign(optimizer, grads)
+
+    def _step_whole(self, plan, kctx, eng, optimizer, red, ls, dyn=None):
+        """one optimizer launch set behind the whole backward pass (or none: the unscaled gradients stay in the engine's flat buffer)"""
+        gs = self._backward_whole(plan, kctx, red, ls)
+        if optimizer is None or not getattr(optimizer, "takes_grad_scale", False):
+            _hand_out_gradients(eng, None, gs)
+            gs = 1.0
+        if optimizer is not None:   # (grad_scale only where there is one to apply: an optimizer without the argument is not handed it)
+            optimizer.step(grads=eng.grad_map(), **({} if gs == 1.0 else {"grad_scale": gs}))
 
     @staticmethod
     def _unscale_for_external_optimizer(eng, dyn, factor):
@@ -627,7 +626,7 @@ class GDRN(nn.Module):
         first GDRN_DP_CHECK_STEPS (default 2) data-parallel steps every rank compares a checksum of its parameters with the other ranks' and
         raises instead of training on silently diverged replicas.  Two host synchronisations in the life of a run."""
         n = self.__dict__.get("_dp_checked", 0)
-        if n >= int(os.environ.get("GDRN_DP_CHECK_STEPS", "2")):
+        if n >= read("GDRN_DP_CHECK_STEPS"):
             return
         import torch.distributed as dist
 
@@ -685,7 +684,7 @@ class GDRN(nn.Module):
         eng.bn_epoch += 1  # the replayed kernels moved the BatchNorm running statistics (run_forward was not called)
         plan.generation += 1  # ... and overwrote the plan's activations: a pending loss.backward() of an earlier model(...) call must not use them
         if optimizer is not None:
-            optimizer.step(grads={eng.P[n]: eng.grads[n] for n in eng.param_names})
+            optimizer.step(grads=eng.grad_map())
         return plan.losses * self._loss_w  # weighted like forward()'s loss_dict
 
     def _maps(self, plan, B):

@@ -6,10 +6,12 @@ status, ``GdrnHipError`` is raised.
 import ctypes as C
 import os
 
+from .switches import read
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("GDRN_HIP_LIB") or os.path.join(_HERE, "lib", "libgdrn_hip.so")   # (GDRN_HIP_LIB: A/B runs of two builds on one box)
+LIB_PATH = read("GDRN_HIP_LIB") or os.path.join(_HERE, "lib", "libgdrn_hip.so")   # (GDRN_HIP_LIB: A/B runs of two builds on one box)
 # the same sources built with IEEE half as the 16-bit format (csrc/common.h): the reference's fp16 autocast arithmetic
-LIB_PATH_F16 = os.environ.get("GDRN_HIP_LIB_F16") or os.path.join(_HERE, "lib", "libgdrn_hip_f16.so")
+LIB_PATH_F16 = read("GDRN_HIP_LIB_F16") or os.path.join(_HERE, "lib", "libgdrn_hip_f16.so")
 
 F32, BF16, F16 = 0, 1, 2
 PREZEROED = 0x100  # GDRN_PREZEROED

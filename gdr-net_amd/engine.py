@@ -22,6 +22,7 @@ import torch
 
 from . import cabi
 from .cabi import BF16, F16, F32, check, ptr
+from .switches import read
 
 RESNET34_LAYERS = (3, 4, 6, 3)
 RESNET34_PLANES = (64, 128, 256, 512)
@@ -55,114 +56,50 @@ class Engine:
     def __init__(self, params, buffers, dtype="bf16", num_regions=64, dry=False, bn_cell=None):
         """params / buffers: dict name -> tensor with the reference's state_dict names.
         dry: build-only engine on host tensors for inspecting the launch lists without a GPU (tests); it cannot run."""
-        # dtype: "bf16" | "fp16" | "fp32".  The 16-bit modes run the same kernels out of two builds of the library (cabi.load)
+        # -- arithmetic and device.  dtype: "bf16" | "fp16" | "fp32"; the 16-bit modes run the same kernels out of two builds of the library (cabi.load)
         self.dt = {"bf16": BF16, BF16: BF16, "fp16": F16, "f16": F16, F16: F16}.get(dtype, F32)
         if self.dt == F32 and dtype not in ("fp32", "f32", F32):
             raise ValueError(f"HIP_DTYPE {dtype!r}: one of bf16, fp16, fp32")
         self.h16 = self.dt != F32          # 16-bit storage / MFMA operands (throughput modes)
         self.lib = cabi.load(self.dt)
-        self.P = params
-        self.Bf = buffers
+        self.P, self.Bf = params, buffers
         self.tdt = {BF16: torch.bfloat16, F16: torch.float16, F32: torch.float32}[self.dt]
         self.esz = 2 if self.h16 else 4
-        # fp16 carries the reference's GradScaler idea (main_gdrn.py:53-56) as a STATIC factor on dL/dloss: the data-gradient chain is stored
-        # in fp16 (6e-5 smallest normal), the fp32 parameter gradients come out multiplied by it and the optimizer's gradient read divides
-        # it out again (Ranger.step(grad_scale=)); 1 for bf16 / fp32
-        # ... and its DYNAMIC part in the fused train step (GDRN.train_step, r5 / ADVICE r4): an inf / NaN anywhere in the step's gradients
-        # (gdrn_nonfinite_flag over the flat buffer) skips the optimizer update and halves the scale, `growth` clean steps in a row double it
-        # again up to 65536 (GradScaler's init_scale).  GDRN_LOSS_SCALE = "<initial scale>[:<growth interval> | :static]", default "1024:2000"
-        # (2000 = GradScaler's growth_interval); ":static" keeps the scale fixed and the optimizer update overlapped with the backward pass
-        import os as _os0
-        ls_spec = (_os0.environ.get("GDRN_LOSS_SCALE", "1024:2000") + ":2000").split(":")
-        # (r6) the dynamic state lives ON THE DEVICE (LossScaleState = gdrn_loss_scale_state): the finite check raises its flag, the fused optimizer
-        # reads flag / scale / step index from it, a one-thread kernel does GradScaler.update's bookkeeping -- no host read in the step; the
-        # properties below (loss_scale, loss_scale_skipped, loss_scale_good) read it back when somebody asks (logging, checkpoints, tests)
-        self._ls_host = float(ls_spec[0]) if self.dt == F16 else 1.0
-        self.loss_scale_dynamic = self.dt == F16 and ls_spec[1] != "static"
-        self.loss_scale_growth = int(ls_spec[1]) if ls_spec[1] != "static" else 0
-        self.ls_state = None   # LossScaleState, made by the first step that needs it (loss_scale_dev)
         self.dev = next(iter(params.values())).device
         self.dry = bool(dry)
         if self.dev.type != "cuda" and not self.dry:
             raise cabi.GdrnHipError("the HIP engine needs parameters on a GPU device (no CPU fallback)")
         self.nreg = num_regions
-        import os as _os
-
-        # 3x3 stride-1 convs (forward and data gradient) on the halo-tiled kernel: the 16-bit modes always.  The fp32 parity mode has the tile
-        # too (8x8 x 64, v_mfma_f32_16x16x4_f32, per-stage partial accumulators: 113-122 TFLOP/s per launch against the generic kernel's ~109,
-        # step 48.1 -> 46.0 ms at bs 64) behind GDRN_HALO_F32: "auto" (default) plans of >= 32 RoIs (both operand layouts are maintained),
-        # "1" every plan, "0" none.  Decided in round 5 AT THE BASELINE SIZE as VERDICT r4 asked (tests/test_e2e_gpu.py::
-        # test_fp32_pose_parity_over_seeds_at_bs64, three seeded bs = 64 batches, against the fp32 AND the fp64 oracle): the two kernels are
-        # equivalent -- R 8.4e-5 / 1.46e-4 / 7.5e-5 (generic) and 8.5e-5 / 1.51e-4 / 7.5e-5 (tile) from the fp32 oracle, 4.6 / 6.4 / 4.4e-5 and
-        # 4.5 / 7.0 / 4.4e-5 from the fp64 one, while the fp32 oracle ITSELF sits 8.0e-5 / 1.02e-4 / 6.7e-5 from fp64: at bs 64 either kernel is
-        # closer to the noise-free value than the reference's own fp32 path, and the 1.5e-4 of seed 2 is that path's noise (one RoI at 5.8e-4).
-        # Plans below 32 RoIs keep the generic kernel: at bs 4 the tile put two of five seeds at 1.02e-4 / 1.17e-4 from the fp32 oracle (generic
-        # <= 9.7e-5) and configs[0] is judged against the fp32 golden.  Operand transforms and the fused BatchNorm-backward epilogue exist for
-        # the 16-bit formats only
-        hf = _os.environ.get("GDRN_HALO_F32", "auto")
-        if hf not in ("auto", "0", "1"):
-            raise ValueError(f"GDRN_HALO_F32={hf!r}: auto, 0 or 1")
+        # -- the switches (switches.TABLE has one line on each, DESIGN.md section 4 what each was measured against), read HERE: an engine keeps
+        # the values it was built with.  Operand transforms and the fused epilogues exist for the 16-bit formats only
+        scale, dynamic, self.loss_scale_growth = read("GDRN_LOSS_SCALE")
+        self._ls_host = scale if self.dt == F16 else 1.0   # static factor on dL/dloss, divided out where the optimizer reads the gradients
+        self.loss_scale_dynamic = self.dt == F16 and dynamic
+        self.ls_state = None   # LossScaleState, made by the first step that needs it (loss_scale_dev)
+        hf = read("GDRN_HALO_F32")
         self.use_halo = self.h16 or hf != "0"
         self.halo_min_b = 1 if (self.h16 or hf == "1") else 32
-        # bucket-end work (grouped weight gradients, their reduction, gradient unpack) on a 2nd stream: it runs under the next bucket's chain of
-        # small-map data-gradient kernels (one workgroup per CU, matrix pipe ~20 % busy); same-box A/B: 8.05 -> 7.85 ms/step with the LDS request
-        # below, 7.77 with the optimizer update of a bucket behind its reduction on that stream (GDRN.train_step, GDRN_EARLY_OPT)
-        # GDRN_WGRAD_STREAM: "1" (default) two streams; "0" one stream; "serial" one stream with the two-stream step's launch configuration
-        # (768 workgroups per grouped weight-gradient launch, the side stream's LDS request = one workgroup per CU) -- the profiling mode:
-        # per-kernel counters and durations then describe the default step's launches without the overlap (tools/gpu_runs/r5_profiles.sh)
-        ws = _os.environ.get("GDRN_WGRAD_STREAM", "1")
-        if ws not in ("0", "1", "serial"):
-            raise ValueError(f"GDRN_WGRAD_STREAM={ws!r}: 1 (two streams), 0 (one stream) or serial (one stream, the two-stream launch configuration)")
-        self.wgrad_stream = ws == "1"
-        self.wgrad_force_lds = ws == "serial"
-        # settled by the A/B measurements of rounds 1-4 (DESIGN.md section 4; their switches are gone with round 5): the last bucket's weight
-        # gradients run under the stem's backward, generic weight / bias gradients go to the side stream too, a side-stream weight-gradient
-        # launch asks for 84 KiB of LDS (one workgroup per CU), the 16-bit modes use the dedicated stem kernels and the split-K fc layers
-        # the head's BatchNorm + ReLU in front of an upsampling evaluated by the upsampling launch, its backward sums by the upsampling's adjoint
-        # (r6, gdrn_bn_relu_upsample2x_fwd / gdrn_upsample2x_bwd_bnsums): "0" = separate launches (A/B, the bit-equality test)
-        self.fuse_up = self.h16 and _os.environ.get("GDRN_FUSE_UP", "1") != "0"
-        # (settled in r6, switches gone: the 16-bit modes run a 64-channel BasicBlock in eval mode as one launch, gdrn_block64_eval, and the 3x3
-        # stride-2 convs and the head's ConvTranspose on the parity-plane / parity-class kernels, gdrn_conv3x3s2 / gdrn_conv3x3s2_dgrad, 8-wide maps
-        # included, wherever the library covers the shape; the generic kernel keeps the rest)
-        self.fc_tail = self.h16 and _os.environ.get("GDRN_FC_TAIL", "1") != "0"   # (A/B, r6) fc2 finish + fc_r | fc_t + pose decode as one launch; seeded train step
-        self.wgrad_side_lds = 84 * 1024
+        self.halo_waves = read("GDRN_HALO_WAVES")
+        self.v3_policy, self.v3_min_wg = read("GDRN_V3")   # (the library reads no environment: the policy travels in gdrn_conv_params)
+        ws = read("GDRN_WGRAD_STREAM")
+        self.wgrad_stream, self.wgrad_force_lds = ws == "1", ws == "serial"
+        self.wgrad_blocks = 1536 if ws == "0" else 768   # target workgroups of a grouped weight-gradient launch: three rounds of what is resident
+        self.wgrad_side_lds = 84 * 1024                  # a side-stream weight-gradient launch asks for one workgroup per CU
+        self.fuse_up = self.h16 and read("GDRN_FUSE_UP")
+        self.fc_tail = self.h16 and read("GDRN_FC_TAIL")
+        self.fuse_xf = self.h16 and read("GDRN_FUSE_XF")
+        self.gemm_bnb = self.h16 and read("GDRN_GEMM_BNB")
         self.stem_direct = self.h16   # the dedicated stem kernels, forward and (fused with bn1's backward apply) weight gradient
         self.stem_w32 = torch.zeros(64 * 7 * 32, dtype=self.tdt, device=self.dev) if self.stem_direct else None
-        # BatchNorm apply passes (forward scale/shift(+residual)+ReLU, backward dx = a*g + b*x + c) evaluated by the CONSUMER halo
-        # conv while it stages its input patch (gdrn_conv_params.xf_*) instead of separate launches; "0" = separate passes (A/B, tests)
-        self.fuse_xf = self.h16 and _os.environ.get("GDRN_FUSE_XF", "1") != "0"
-        # (every transform mode, on every map size: r2's policy sweep by mode and by largest feature-map side -- all-fused won)
-        # BatchNorm-backward mask + sums also in the generic kernel's epilogue (1x1 output conv, stride-2 / transposed data gradients)
-        self.gemm_bnb = self.h16 and _os.environ.get("GDRN_GEMM_BNB", "1") == "1"
-        self.halo_waves = int(_os.environ.get("GDRN_HALO_WAVES", "0"))   # A/B: 4 / 8 force the four- / eight-wave form of the first halo kernel's 128-channel tile
-        # second-generation halo kernel (conv3x3_v3.hip): GDRN_V3 = "0" never, "2" wherever it covers the shape (the 256-channel tile also on
-        # small grids) -- A/B and the plan variants of tests/test_teacher_forced_gpu.py; default: where the library measured it faster.  The
-        # library itself reads no environment: the policy travels in gdrn_conv_params (w_frag of the gdrn_conv3x3_wfrag query, v3_min_wg)
-        v3 = _os.environ.get("GDRN_V3", "")
-        if v3 not in ("", "0", "2"):
-            raise ValueError(f"GDRN_V3={v3!r}: 0 (never), 2 (wherever covered) or unset")
-        self.v3_policy = {"": 0, "0": 1, "2": 2}[v3]
-        self.v3_min_wg = 1 if v3 == "2" else 0
-        # target workgroups of a grouped weight-gradient launch = three rounds of what is resident: one stream, 2 per CU = 512 per round
-        # (measured 512: 8.70, 1024: 8.13, 1536: 8.09, 2048: 8.28 ms/step); side stream, 1 per CU = 256 per round (r3: 512: 8.02, 768: 7.575,
-        # 1024: 7.54, 1280: 7.615, 1536: 7.58 -- 768 writes half the partial tiles of 1536 for the same step time)
-        #  Rejected by measurement and removed from the engine in round 5 (DESIGN.md section 4 has the figures): extra cuts of the grouped
-        #  launches inside a bucket, a third stream for the HBM-bound bucket tails, the 128 x 64 weight-gradient tile (the kernel stays in the
-        #  library behind gdrn_wgrad_params.variant, with its kernel tests)
-        #  (extra launch groups of the grouped weight gradient were measured again in r6: no gain.  Small side-stream ops wait for their
-        #  bucket's end, Plan._merge_forks: 6 instead of 11 stream switches per backward pass -- r6: no measurable effect on the step, kept)
-        self.wgrad_blocks = 768 if (self.wgrad_stream or self.wgrad_force_lds) else 1536
-        nb = _os.environ.get("GDRN_BUCKETS")
+        nb = read("GDRN_BUCKETS")
         self.buckets_from_env = nb is not None
         if nb is None:
             import torch.distributed as _dist
 
-            # (with the side stream: a fifth bucket layer2 | layer1 + stem measured +0.12 ms, layer2 moved into the layer4 + layer3 bucket
-            #  +0.11 ms -- a weight gradient at one workgroup per CU wants a chain at least 1.7x its stand-alone time to hide under)
             nb = 5 if (_dist.is_available() and _dist.is_initialized() and _dist.get_world_size() > 1) else 4
-        if str(nb) not in ("4", "5"):
-            raise ValueError(f"GDRN_BUCKETS={nb!r}: the gradient bucket layouts are 4 (one GPU) and 5 (data parallel)")
-        self.bucket_first_group, self.bucket_marks = BUCKET_LAYOUTS[int(nb)]
+        self.bucket_first_group, self.bucket_marks = BUCKET_LAYOUTS[nb]
+        self.max_plans = read("GDRN_MAX_PLANS")
+        # -- layers, plans, gradients
         self.layers = OrderedDict()
         self._versions = {}
         self.bn_fold = {}  # bn key -> NS(scale, shift, layer): eval-mode BatchNorm folded into the preceding conv (every eval plan)
@@ -171,18 +108,19 @@ class Engine:
         self._bn_cell = bn_cell if bn_cell is not None else [0]
         self._build_layers()
         self.plans = OrderedDict()   # (batch size, train-mode BatchNorm, losses) -> Plan, least recently used first
-        self.max_plans = int(_os.environ.get("GDRN_MAX_PLANS", "8"))
         self.plan_builds = 0
         self.param_names = list(self.P.keys())
-        # flat fp32 gradient buffer, ordered by backward completion (reverse of forward order)
-        order = list(reversed(self.param_names))
+        self._grad_layout()
+
+    def _grad_layout(self):
+        """the flat fp32 gradient buffer, ordered by backward completion (reverse of forward order), every parameter's view into it, the buckets"""
         self.grad_offsets = {}
         off = 0
         # fc_r | fc_t run as ONE 9-row layer (fc_rt): their bias gradients share one slot, fc_t's right behind fc_r's, so that the layer's single
         # bias_grad launch writes both in place (every reader -- Ranger, the collectives, .grad -- takes offset + numel, not padded rows)
         rb, tb = "pnp_net.fc_r.bias", "pnp_net.fc_t.bias"
         paired = rb in self.P and tb in self.P
-        for n in order:
+        for n in reversed(self.param_names):
             if paired and n in (rb, tb):
                 if rb not in self.grad_offsets:
                     self.grad_offsets[rb] = off
@@ -195,6 +133,10 @@ class Engine:
         self.grads = {n: self.grad_flat[self.grad_offsets[n]: self.grad_offsets[n] + self.P[n].numel()].view(self.P[n].shape)
                       for n in self.param_names}
         self.bucket_bounds = self._bucket_bounds()
+
+    def grad_map(self):
+        """parameter -> its gradient view in the flat buffer, what the optimizers take as `grads=` (built on each call)"""
+        return {self.P[n]: self.grads[n] for n in self.param_names}
 
     # ------------------------------------------------------------------------------------------ fp16 loss scale
     @property
@@ -395,8 +337,6 @@ class Engine:
 
     def eval_refresh(self):
         """(Re)compute the folded scale / shift vectors and the scaled operand copies; the caller decides when."""
-        from .cabi import PackTask, to_device_table
-
         lib, st = self.lib, self._stream()
         if not self.bn_fold:
             return
@@ -413,11 +353,11 @@ class Engine:
                     A1, A2, T, B, A1v, A2v, Bv, s1, s2, stt, sb, flip = self._pack_args(L, "f")
                     kch = B * (2 if self.h16 else 4) // 128
                     sh = (kch.bit_length() if (frag and kch > 0 and kch & (kch - 1) == 0) else 0)
-                    t = PackTask(src=src.data_ptr(), dst=dst.data_ptr(), scale=f.scale.data_ptr(), A1=A1, A2=A2, T=T, B=B, A1v=A1v,
+                    t = cabi.PackTask(src=src.data_ptr(), dst=dst.data_ptr(), scale=f.scale.data_ptr(), A1=A1, A2=A2, T=T, B=B, A1v=A1v,
                                  A2v=A2v, Bv=Bv, flip=flip, s1=s1, s2=s2, st=stt, sb=sb, n=A1 * A2 * T * B, frag=frag, pad_=sh)
                     tasks.append(t)
                     starts.append(starts[-1] + ((A1 // 16) * (B // 64) if (frag and self.h16) else (t.n + chunk - 1) // chunk))
-            self._eval_tab = (to_device_table(tasks, self.dev), torch.tensor(starts, dtype=torch.int32, device=self.dev), len(tasks), starts[-1])
+            self._eval_tab = (cabi.to_device_table(tasks, self.dev), torch.tensor(starts, dtype=torch.int32, device=self.dev), len(tasks), starts[-1])
         for bnkey, f in self.bn_fold.items():
             g, b = self.P[bnkey + ".weight"], self.P[bnkey + ".bias"]
             rm, rv = self.Bf[bnkey + ".running_mean"], self.Bf[bnkey + ".running_var"]
@@ -427,8 +367,6 @@ class Engine:
 
     def _build_pack_table(self):
         """Device task table for gdrn_pack_multi: every operand copy of every layer (stem excluded) in ONE launch."""
-        from .cabi import PackTask, to_device_table
-
         chunk = self.lib.gdrn_pack_chunk()
         tasks, starts = [], [0]
         for key, L in self.layers.items():
@@ -442,14 +380,14 @@ class Engine:
                 A1, A2, T, B, A1v, A2v, Bv, s1, s2, st, sb, flip = self._pack_args(L, which)
                 kch = B * (2 if self.h16 else 4) // 128  # 128-byte chunks per pixel row
                 sh = (kch.bit_length() if (frag and kch > 0 and kch & (kch - 1) == 0) else 0)  # 1 + log2(kch)
-                t = PackTask(src=src.data_ptr(), dst=dst.data_ptr(), A1=A1, A2=A2, T=T, B=B, A1v=A1v, A2v=A2v, Bv=Bv, flip=flip,
+                t = cabi.PackTask(src=src.data_ptr(), dst=dst.data_ptr(), A1=A1, A2=A2, T=T, B=B, A1v=A1v, A2v=A2v, Bv=Bv, flip=flip,
                              s1=s1, s2=s2, st=st, sb=sb, n=A1 * A2 * T * B, frag=frag, pad_=sh)
                 tasks.append(t)
                 # workgroups of the task: bf16 fragment-major operands go brick by brick (16 rows x 64 b x 9 taps); row-major copies whose
                 # unit-stride source index is not b (fc1's two operands, the 1x1 / fc data-gradient operands) as 64 x 64 tiles through LDS (r6)
                 nblk = (A1 // 16) * (B // 64) if (frag and self.h16) else (cabi.transpose_blocks(self.lib, t) or (t.n + chunk - 1) // chunk)
                 starts.append(starts[-1] + nblk)
-        self._pack_tasks = to_device_table(tasks, self.dev)
+        self._pack_tasks = cabi.to_device_table(tasks, self.dev)
         self._pack_starts = torch.tensor(starts, dtype=torch.int32, device=self.dev)
         self._pack_n = (len(tasks), starts[-1])
         # the same tasks per gradient bucket (repack_bucket): the fused train step rebuilds a bucket's operands right behind its optimizer update
@@ -467,7 +405,7 @@ class Engine:
             st_ = [0]
             for _, n in sel:
                 st_.append(st_[-1] + n)
-            self._pack_buckets.append((to_device_table([t for t, _ in sel], self.dev), torch.tensor(st_, dtype=torch.int32, device=self.dev), len(sel), st_[-1]))
+            self._pack_buckets.append((cabi.to_device_table([t for t, _ in sel], self.dev), torch.tensor(st_, dtype=torch.int32, device=self.dev), len(sel), st_[-1]))
 
     def repack(self, force=False):
         """(Re)build the kernel-layout operand copies of the weights after a parameter update: one multi-tensor

@@ -10,7 +10,7 @@ import ctypes
 import math
 
 import torch
-from torch.optim.optimizer import Optimizer
+from torch.optim import optimizer as _torch_optimizer   # (the module: torch.optim does not keep it as an attribute)
 
 from . import cabi
 
@@ -22,20 +22,9 @@ def _bump_version(t):
         t.add_(0)
 
 
-def _global_pre_hooks():
-    try:
-        from torch.optim.optimizer import _global_optimizer_pre_hooks
-        return _global_optimizer_pre_hooks.values()
-    except ImportError:   # private name: absent -> no global hooks to fire
-        return ()
-
-
-def _global_post_hooks():
-    try:
-        from torch.optim.optimizer import _global_optimizer_post_hooks
-        return _global_optimizer_post_hooks.values()
-    except ImportError:
-        return ()
+def _global_hooks(when):
+    """torch's process-wide optimizer step hooks, when = "pre" | "post" (a private name: absent -> no global hooks to fire)"""
+    return list(getattr(_torch_optimizer, f"_global_optimizer_{when}_hooks", {}).values())
 
 
 def radam_step_size(step, beta1, beta2, n_sma_threshold):
@@ -56,7 +45,7 @@ _TASK_WORDS = ctypes.sizeof(cabi.RangerTask) // 4  # gdrn_ranger_task as 32-bit 
 _LR_WORD = cabi.RangerTask.lr.offset // 4
 
 
-class Ranger(Optimizer):
+class Ranger(_torch_optimizer.Optimizer):
     takes_grad_scale = True  # step(grad_scale=): GDRN.train_step folds the 1/world of a SUM all-reduce into the kernel
 
     def __init__(self, params, lr=1e-3, alpha=0.5, k=6, N_sma_threshhold=5, betas=(0.95, 0.999), eps=1e-5, weight_decay=0,
@@ -126,6 +115,32 @@ class Ranger(Optimizer):
         cache[gi] = (key, tab, stt, len(tasks), starts[-1], lr)
         return cache[gi][1:5]
 
+    def _fused_groups(self, grads):
+        """[(group index, group, [(param, fp32 gradient)], [state])] of the param groups with gradients in `grads`, for the multi-tensor launches"""
+        # None: those do not apply -- a tensor off the GPU, not fp32 or not contiguous, or a group whose tensors are at different step counts
+        plan = []
+        for gi, group in enumerate(self.param_groups):
+            items = [(p, grads[p].detach()) for p in group["params"] if grads.get(p) is not None]
+            if not items:
+                continue
+            if any(p.device.type != "cuda" or p.dtype != torch.float32 or g.dtype != torch.float32 or not g.is_contiguous() for p, g in items):
+                return None
+            states = [self._init_state(p) for p, _ in items]
+            if len({s["step"] for s in states}) != 1:
+                return None
+            plan.append((gi, group, items, states))
+        return plan
+
+    def _fire_pre(self):
+        """the hooks torch fires in front of optimizer.step()"""
+        for hook in _global_hooks("pre") + list(getattr(self, "_optimizer_step_pre_hooks", {}).values()):
+            hook(self, (), {})
+
+    def _fire_post(self, **kw):
+        """... and behind it; kw: what the hook is handed as the step's keyword arguments"""
+        for hook in list(getattr(self, "_optimizer_step_post_hooks", {}).values()) + _global_hooks("post"):
+            hook(self, (), kw)
+
     # ---- per-bucket stepping: the fused train step (GDRN.train_step) launches the update of a gradient bucket on the side stream as soon
     # as that bucket's gradients are complete, under the rest of the backward pass, instead of three launches behind it
     @torch.no_grad()
@@ -134,25 +149,15 @@ class Ranger(Optimizer):
         bucket) for the NEXT step index; the step counters themselves advance in step_buckets_end.  False: the per-bucket path does not
         apply (mixed step counts, CPU parameters, ...) and nothing was changed -- call step()."""
         self._leave_dyn()
-        plan = []
-        for gi, group in enumerate(self.param_groups):
-            items = [(p, grads[p].detach()) for p in group["params"] if grads.get(p) is not None]
-            if not items:
-                continue
-            if any(p.device.type != "cuda" or p.dtype != torch.float32 or g.dtype != torch.float32 or not g.is_contiguous() for p, g in items):
-                return False
-            states = [self._init_state(p) for p, _ in items]
-            if len({s["step"] for s in states}) != 1:
-                return False
-            plan.append((gi, group, items, states))
-        lib = cabi.load()
+        plan = self._fused_groups(grads)
+        if plan is None:
+            return False
+        self._bucket_lib = cabi.load()
         self._check_not_poisoned()
         self._bucket_launches = [[] for _ in range(nbuckets)]
-        self._bucket_done = 0
-        self._bucket_params = []
-        self._bucket_states = []   # their step counters advance in step_buckets_end: an exception inside the backward pass leaves them alone
-        for hook in list(_global_pre_hooks()) + list(getattr(self, "_optimizer_step_pre_hooks", {}).values()):
-            hook(self, (), {})     # the hooks torch fires around optimizer.step()
+        # (the step counters of _bucket_states advance in step_buckets_end: an exception inside the backward pass leaves them alone)
+        self._bucket_done, self._bucket_params, self._bucket_states = 0, [], []
+        self._fire_pre()
         for gi, group, items, states in plan:
             self._bucket_states += states
             step = states[0]["step"] + 1
@@ -166,7 +171,6 @@ class Ranger(Optimizer):
                 self._bucket_launches[b].append((tab, stt, nt, nrows, beta1, beta2, group["eps"], group["weight_decay"], step_size,
                                                  1 if n_sma > self.N_sma_threshhold else 0, 1 if step % group["k"] == 0 else 0, float(grad_scale)))
             self._bucket_params += [p for p, _ in items]
-        self._bucket_lib = lib
         return True
 
     def step_bucket(self, b):
@@ -186,8 +190,7 @@ class Ranger(Optimizer):
             _bump_version(p)  # updated in place behind autograd's back: tell repack() the weights changed
         self._bucket_launches, self._bucket_params, self._bucket_states = [], [], []
         self._opt_called = True
-        for hook in list(getattr(self, "_optimizer_step_post_hooks", {}).values()) + list(_global_post_hooks()):
-            hook(self, (), {})
+        self._fire_post()
 
     def reset_after_abort(self):
         """the caller has restored BOTH the model's parameters and this optimizer's state (load_state_dict on each) after an aborted per-bucket
@@ -207,8 +210,7 @@ class Ranger(Optimizer):
         if getattr(self, "_bucket_done", 0) > 0:
             self._buckets_poisoned = True
         self._bucket_launches, self._bucket_params, self._bucket_states = [], [], []
-        for hook in list(getattr(self, "_optimizer_step_post_hooks", {}).values()) + list(_global_post_hooks()):
-            hook(self, (), {"aborted": True})   # (the partner of the pre-hook; the marker tells a step-counting hook that no step completed)
+        self._fire_post(aborted=True)   # (the partner of the pre-hook; the marker tells a step-counting hook that no step completed)
 
     # ---- fp16 arithmetic mode with the dynamic loss scale on the device (r6): no host read between the backward pass and the update
     @torch.no_grad()
@@ -218,25 +220,16 @@ class Ranger(Optimizer):
         state's scale, and evaluates RAdam's step size / rectification / lookahead phase at base_step + applied + 1 -- the count of APPLIED
         steps, kept on the device.  The host's state["step"] counters are NOT advanced here: sync_dyn() (called by state_dict()) reads them back.
         The caller launches gdrn_loss_scale_update behind this.  False: the per-group multi-tensor path does not apply -- nothing was launched."""
-        plan = []
-        for gi, group in enumerate(self.param_groups):
-            items = [(p, grads[p].detach()) for p in group["params"] if grads.get(p) is not None]
-            if not items:
-                continue
-            if any(p.device.type != "cuda" or p.dtype != torch.float32 or g.dtype != torch.float32 or not g.is_contiguous() for p, g in items):
-                return False
-            states = [self._init_state(p) for p, _ in items]
-            plan.append((gi, group, items, states))
-        steps = {s["step"] for _, _, _, states in plan for s in states}
-        if len(steps) != 1:
+        plan = self._fused_groups(grads)
+        steps = {states[0]["step"] for _, _, _, states in plan or ()}
+        if len(steps) != 1:   # (one step index on the device: every group at the same count)
             return False
         if getattr(self, "_dyn", None) is not dyn:
             dyn.write(base_step=steps.pop())   # (re)base: device step index = these counters + steps applied from here on
             self._dyn = dyn
         lib = cabi.load()
         st = torch.cuda.current_stream().cuda_stream
-        for hook in list(_global_pre_hooks()) + list(getattr(self, "_optimizer_step_pre_hooks", {}).values()):
-            hook(self, (), {})
+        self._fire_pre()
         for gi, group, items, states in plan:
             beta1, beta2 = group["betas"]
             tab, stt, nt, nrows = self._multi_table(("dyn", gi), items, float(group["lr"]))
@@ -245,8 +238,7 @@ class Ranger(Optimizer):
             for p, _ in items:
                 _bump_version(p)   # (possibly) updated in place behind autograd's back
         self._opt_called = True
-        for hook in list(getattr(self, "_optimizer_step_post_hooks", {}).values()) + list(_global_post_hooks()):
-            hook(self, (), {})
+        self._fire_post()
         return True
 
     def sync_dyn(self):

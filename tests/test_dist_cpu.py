@@ -88,7 +88,7 @@ def _worker_autograd(rank, world, port, q):
             flat = torch.zeros(40)
             offs = {"b.bias": 0, "a.weight": 8}  # backward-completion order: b first
             grads = {n: flat[offs[n]: offs[n] + params[n].numel()].view(params[n].shape) for n in names}
-            eng = NS(grads=grads, param_names=names, grad_flat=flat, P=params)
+            eng = NS(grads=grads, param_names=names, grad_flat=flat, P=params, loss_scale_dev=lambda: None, _ls_host=1.0)   # (no loss scale: bf16 / fp32)
             bounds = [(0, 8), (8, 40)]
             red = GradReducer(flat, bounds, average=True, comm_dtype=comm, defer_scale=True)
             model = NS(_on_bucket=red.on_bucket, _reducer=red)

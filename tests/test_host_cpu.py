@@ -256,7 +256,7 @@ def _dry_engine(dtype="bf16"):
 
 
 def test_engine_switches_are_validated_and_the_library_reads_no_environment(monkeypatch):
-    """r5: 15 documented switches, every one of them read by the Python host with a checked value set; the C-ABI library
+    """r5: 18 documented switches, every one of them read by the Python host with a checked value set; the C-ABI library
     itself calls getenv nowhere -- its choices are functions of the params (host-only queries below, no GPU)."""
     import glob
 
@@ -297,6 +297,76 @@ def test_engine_switches_are_validated_and_the_library_reads_no_environment(monk
     k64 = {getattr(op, "meta", {}).get("kernel") for op in e.plan(64, True, True).fwd}
     k4 = {getattr(op, "meta", {}).get("kernel") for op in e.plan(4, True, True).fwd}
     assert any(k and k.startswith("conv3x3_halo_kernel<f32") for k in k64) and not any(k and k.startswith("conv3x3_halo_kernel") for k in k4)
+
+
+def test_switch_table_is_the_documented_one_and_the_only_reader_of_the_environment(monkeypatch):
+    """gdrnet_amd.switches: its table names exactly the variables of INTEGRATION.md section 3 (one row each, the heading counts them), no other
+    module of the package looks a GDRN_* name up in the environment, and every switch read by the engine's constructor refuses an undocumented
+    value with a ValueError that names the variable."""
+    import glob
+
+    from gdrnet_amd import switches
+    from gdrnet_amd.engine import Engine
+
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = doc[doc.index("## 3. Environment switches"):doc.index("## 4. ")]
+    rows = [[c.strip() for c in re.split(r"(?<!\\)\|", ln)[1:-1]] for ln in sec.splitlines() if ln.startswith("| `GDRN_")]   # variable | default | read at | effect
+    names = [re.match(r"`(GDRN_[A-Z0-9_]+)`", r[0]).group(1) for r in rows]
+    assert sorted(names) == sorted(switches.TABLE) and len(names) == len(set(names))
+    assert int(re.match(r"## 3\. Environment switches \((\d+);", sec).group(1)) == len(names)
+    assert [r[2] for r in rows] == [switches.TABLE[n].read_at for n in names]
+    near = re.compile(r"\benviron\b[^\n]*GDRN_[A-Z0-9_]+|GDRN_[A-Z0-9_]+[^\n]*\benviron\b")   # on one line with os.environ
+    hits = [os.path.basename(f) for f in glob.glob(os.path.join(ROOT, "gdr-net_amd", "*.py")) if near.search(open(f).read())]
+    assert set(hits) <= {"switches.py"}, hits
+    bad = {"GDRN_WGRAD_STREAM": "2", "GDRN_HALO_F32": "yes", "GDRN_V3": "1", "GDRN_BUCKETS": "3", "GDRN_GEMM_BNB": "yes", "GDRN_FUSE_XF": "2",
+           "GDRN_HALO_WAVES": "6", "GDRN_FUSE_UP": "on", "GDRN_FC_TAIL": "", "GDRN_MAX_PLANS": "0", "GDRN_LOSS_SCALE": "1024:often"}
+    assert set(bad) == {s.name for s in switches.TABLE.values() if s.read_at == switches.ENGINE}
+    params, buffers = {"backbone.conv1.weight": torch.zeros(64, 3, 7, 7)}, {}   # (the constructor reads its switches before it looks at a layer)
+    for var, value in bad.items():
+        monkeypatch.setenv(var, value)
+        with pytest.raises(ValueError, match=var):
+            Engine(params, buffers, dtype="bf16", dry=True)
+        monkeypatch.delenv(var)
+    for var, value in (("GDRN_EARLY_OPT", "yes"), ("GDRN_GRAPH", "2"), ("GDRN_DP_CHECK_STEPS", "-1"), ("GDRN_HIP_DTYPE", "fp8")):
+        monkeypatch.setenv(var, value)
+        with pytest.raises(ValueError, match=var):
+            switches.read(var)
+        monkeypatch.delenv(var)
+    assert switches.read("GDRN_EARLY_OPT") is True and switches.read("GDRN_GRAPH") is False and switches.read("GDRN_DP_CHECK_STEPS") == 2
+
+
+def test_update_schedule_truth_table(monkeypatch):
+    """GDRN._update_schedule, the decision of train_step's three tails, row by row as train_step's expression had it before the split: the
+    per-bucket update needs an optimizer that has it, two streams, GDRN_EARLY_OPT, and either nothing attached or the model's own deferred-scale
+    reducer (on the GPU, or inactive); a dynamic loss-scale state overrides everything."""
+    from types import SimpleNamespace as NS
+
+    from gdrnet_amd.GDRN import _update_schedule
+
+    monkeypatch.delenv("GDRN_EARLY_OPT", raising=False)
+    ranger, sgd = NS(step_buckets_begin=None, step=None), NS(step=None)
+    two, one = NS(wgrad_stream=True), NS(wgrad_stream=False)
+    hook = lambda b: None
+
+    def red(**kw):
+        return NS(**dict(dict(on_bucket=hook, defer_scale=True, cuda=True, active=True), **kw))
+
+    assert _update_schedule(ranger, None, None, two, None) == "per_bucket"
+    assert _update_schedule(ranger, None, None, one, None) == "whole"              # GDRN_WGRAD_STREAM=0 / serial
+    assert _update_schedule(None, None, None, two, None) == "whole"
+    assert _update_schedule(sgd, None, None, two, None) == "whole"                 # no step_buckets_begin
+    assert _update_schedule(ranger, red(), hook, two, None) == "per_bucket"        # the model's reducer, on the GPU
+    assert _update_schedule(ranger, red(defer_scale=False), hook, two, None) == "whole"
+    assert _update_schedule(ranger, red(), lambda b: None, two, None) == "whole"   # somebody else's hook
+    assert _update_schedule(ranger, red(cuda=False), hook, two, None) == "whole"   # active reducer off the GPU
+    assert _update_schedule(ranger, red(cuda=False, active=False), hook, two, None) == "per_bucket"
+    assert _update_schedule(ranger, None, hook, two, None) == "whole"              # on_bucket set without a reducer
+    dyn = NS(ptr=0)
+    for args in ((ranger, None, None, two), (None, None, None, one), (sgd, red(cuda=False), hook, one), (ranger, None, hook, two)):
+        assert _update_schedule(*args, dyn) == "guarded"
+    monkeypatch.setenv("GDRN_EARLY_OPT", "0")
+    assert _update_schedule(ranger, None, None, two, None) == "whole" and _update_schedule(ranger, red(), hook, two, None) == "whole"
+    assert _update_schedule(ranger, None, None, two, dyn) == "guarded"
 
 
 def test_kernel_form_and_layout_queries_are_functions_of_the_params():

@@ -87,6 +87,9 @@ def test_configurations_cover_every_engine_switch():
     names = [c[0] for c in PT.CONFIGS]
     assert len(names) == len(set(names)) == 48 + 11 + 2
     varied = {k for c in PT.CONFIGS for k in c[5]}
+    from gdrnet_amd import switches
+
     src = open(os.path.join(ROOT, "gdr-net_amd", "engine.py")).read()
-    read = set(re.findall(r'environ\.get\("(GDRN_[A-Z0-9_]+)"', src))
+    read = set(re.findall(r'\bread\("(GDRN_[A-Z0-9_]+)"', src))   # what the engine reads is what the table says it reads
+    assert read == {s.name for s in switches.TABLE.values() if s.read_at == switches.ENGINE} and len(read) == 11
     assert read - varied == {"GDRN_MAX_PLANS", "GDRN_LOSS_SCALE"}, read - varied   # (plan cache size, fp16 loss scale: no launch list depends on them)
